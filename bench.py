@@ -14,8 +14,21 @@ of pixel-tile rows, the frame's new keys and the carve candidates are all-gather
 each rank updates only its own blocks. value = frames / max rank time, scaling "strong"; the volume
 is the single-GPU volume block for block. --mode sharded: the same with every rank running the whole
 DDA (no key exchange). --mode streams: each rank integrates its own camera stream into its own volume
-(a multi-camera rig; weak scaling, no data-path collective). At N>1 the line carries the streams run
-as a labelled "secondary" object measured in the same job (--secondary none to skip).
+(a multi-camera rig; weak scaling, no data-path collective).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.
+Every measurement beside the headline figure that takes a run of its own is made only with --full:
+the CPU baseline, the C++ loop (cpp_loop), the C5 raycast timing, the --host-frames upload timing and,
+at N>1, the streams run (a labelled "secondary" object measured in the same job, --secondary none to
+skip) and the frame broadcast timing. The roofline below comes from the timed steps themselves and
+is part of every line.
+
+--dump-outputs DIR: after the timed steps, what the last timed step left for a caller, as float32 /
+float64 .npy files (rank 0): the voxels (tsdf, prob, rgbw) at a fixed, seeded sample of voxel
+coordinates around the last frame's surface (voxel_xyz), the volume's counts (counts: active blocks,
+the last frame's visible blocks and updated voxels) and, in the C5 loop, the last raycast's images
+(raycast_rgba, raycast_normal) and triangle count (mesh_triangles). The frames are seeded, so the same
+arguments give the same inputs run after run and two builds compare file for file.
 
 roofline: SURVEY.md 8d. The frame-level fraction B_read * frames/s / (N * 8 TB/s) with
 B_read = 15 W H (frame) + N_vis * 6156 B (voxel state + metadata of every visible block), and the
@@ -27,7 +40,7 @@ MI355X_MICROARCH.md gfx950 corrections) of THIS command over the same timed-wind
 accepted only when that pass integrated the same frames (equal N_vis / N_upd sums); otherwise null.
 The two resolvers run inside the ingest / update kernels' last-arriving workgroups: their device-clock
 spans are reported in "device_us_per_frame".
-cpu_baseline: the single-threaded CPU oracle (oracle/tsdf_oracle.c, a restatement of the reference
+cpu_baseline (--full): the single-threaded CPU oracle (oracle/tsdf_oracle.c, a restatement of the reference
 kernels incl. its full-table visibility scan) on the first frames of this same stream (the GPU
 frames copied to the host), from an empty map.
 """
@@ -66,7 +79,7 @@ def parse():
                    help="N>1: routed (sharded volume, DDA split by tile rows, keys exchanged), sharded "
                         "(sharded volume, whole-frame DDA on every rank), streams (one volume per rank)")
     p.add_argument("--secondary", choices=("streams", "none"), default="streams",
-                   help="N>1: also measure the streams mode in the same job (labelled secondary)")
+                   help="N>1 with --full: also measure the streams mode in the same job (labelled secondary)")
     p.add_argument("--loop", choices=("c3", "c5"), default="c3",
                    help="c5: BASELINE config C5 -- integrate + raycast of the frame's camera every frame, "
                         "marching cubes of the whole volume every 30 frames (eager chain)")
@@ -83,12 +96,19 @@ def parse():
                    help="sharded modes: key records per rank per frame (0 = 32768 / G)")
     p.add_argument("--cand-cap", type=int, default=0,
                    help="sharded modes: carve-candidate records per rank per frame (0 = 16384 / G)")
-    p.add_argument("--cpu-frames", type=int, default=-1, help="oracle sample size (-1 = auto)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the C++ loop, the "
+                        "C5 raycast timing, the --host-frames upload timing, the N>1 secondary streams run "
+                        "and frame broadcast timing")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                        "(float32 / float64; a fixed, seeded sample of the volume)")
+    p.add_argument("--cpu-frames", type=int, default=-1, help="--full: oracle sample size (-1 = auto)")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--native-group", action="store_true",
                    help="with --shard G: the library-owned group (tsdf_group_*) instead of tsdf_amd.ShardGroup")
     p.add_argument("--no-cpp-loop", action="store_true",
-                   help="skip the C++ timed loop over the C ABI (disinfect-slam_amd/bench_main) that the "
+                   help="--full: skip the C++ timed loop over the C ABI (disinfect-slam_amd/bench_main) that the "
                         "single-GPU C3 line runs after its own loop (the host enqueue floor without Python)")
     p.add_argument("--broadcast-frames", dest="broadcast_frames", action="store_true", default=None,
                    help="sharded modes: rank 0 broadcasts every frame to the other ranks inside the timed "
@@ -447,7 +467,7 @@ def main():
     if a.host_frames:
         if world > 1:
             raise SystemExit("--host-frames is a single-GPU line")
-        frames, upload = host_frames(a, frames)
+        frames, upload = host_frames(a, frames, time_upload=a.full)
     run = Run(a, mode, rank, world, dev, cam, frames, K, poses, dist)
     elapsed, prof = run.timed()
     st = run.eng.stats()
@@ -476,7 +496,11 @@ def main():
     frame_frac_rw = (b_read + b_write) * steps_per_s / (world * HBM_PEAK_GBS * 1e9)
     mesh_tris = run.mesh_tris[-1] if run.mesh_tris else None
     ray = None
-    if a.loop == "c5" and not run.sharded:
+    if a.dump_outputs and rank == 0:  # before anything else touches the volume or the images
+        dump_outputs(a, [run.eng], run.frame_views["depth"][nframes - 1],
+                     tdist.stream_offset(mode, rank, world) + nframes - 1,
+                     images={"raycast_rgba": run.rgba, "raycast_normal": run.normal}, mesh_tris=run.mesh_tris)
+    if a.full and a.loop == "c5" and not run.sharded:
         ray = raycast_roofline(a, run.raycast_timing())
     host_enq = run.host_enqueue_ms
     exch = None
@@ -490,7 +514,7 @@ def main():
     del frames
 
     secondary = None
-    if world > 1 and a.secondary == "streams" and mode != "streams":
+    if a.full and world > 1 and a.secondary == "streams" and mode != "streams":
         fr2, po2 = stream_frames("streams")
         torch.cuda.synchronize()
         r2 = Run(a, "streams", rank, world, dev, cam, fr2, K, po2, dist)
@@ -503,13 +527,14 @@ def main():
                              "rig; no data-path collective); value = all ranks' frames / max rank time"}
 
     bcast = None
-    if world > 1 and mode in ("routed", "sharded"):
+    if a.full and world > 1 and mode in ("routed", "sharded"):
         bcast = frame_broadcast_ms(a, dist, None, dev)
     cpp = None
-    if rank == 0 and world == 1 and a.loop == "c3" and not a.graph and not a.host_frames and not a.no_cpp_loop:
+    if (a.full and rank == 0 and world == 1 and a.loop == "c3" and not a.graph and not a.host_frames
+            and not a.no_cpp_loop):
         cpp = cpp_loop(a, cam, nframes)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         fr_host = synth.render_torch(cam, list(range(0, min(nframes, 80))), device=dev)
         cpu = cpu_baseline(a, cam, fr_host)
 
@@ -578,6 +603,7 @@ def main():
             "scaling": "weak" if mode == "streams" else ("strong" if world > 1 else "weak"),
             "vs_baseline": None,
             "dtype": "f32",
+            "full": bool(a.full),
             "data": "synthetic (analytic room scene rendered on GPU, resident in HBM)",
             "config": {
                 "workload": workload_name(a),
@@ -655,10 +681,11 @@ def cpp_loop(a, cam, nframes):
         shutil.rmtree(d, ignore_errors=True)
 
 
-def host_frames(a, fr, reps=20):
+def host_frames(a, fr, time_upload, reps=20):
     """--host-frames: the stream's frames copied to host memory (pageable numpy arrays, or pinned torch
-    tensors), and the upload alone timed: `reps` uploads of one frame's four arrays (rgb u8, depth /
-    ht / lt f32) into device buffers on a side stream, between events -- the PCIe share of a frame."""
+    tensors), and -- time_upload (--full) -- the upload alone timed: `reps` uploads of one frame's four
+    arrays (rgb u8, depth / ht / lt f32) into device buffers on a side stream, between events -- the
+    PCIe share of a frame."""
     import numpy as np
     import torch
     keys = ("rgb", "depth") + (() if a.depth_only else ("ht", "lt"))
@@ -667,6 +694,8 @@ def host_frames(a, fr, reps=20):
         t = fr[k].cpu()
         out[k] = [t[i].pin_memory() for i in range(t.shape[0])] if a.host_frames == "pinned" else \
                  [np.ascontiguousarray(t[i].numpy()) for i in range(t.shape[0])]
+    if not time_upload:
+        return out, None
     dst = {k: torch.empty_like(fr[k][0]) for k in keys}
     src = {k: (out[k][0] if a.host_frames == "pinned" else torch.from_numpy(out[k][0])) for k in keys}
     st = torch.cuda.Stream()
@@ -689,6 +718,59 @@ def host_frames(a, fr, reps=20):
                          f"{reps} reps; the line's value includes the engine's own "
                          "uploads (copies over two upload streams, overlapped with the previous frames' kernels; "
                          "each call returns once its frame's copies are complete)"}
+
+
+DUMP_SEED = 0x5EED
+DUMP_PIXELS = 32768  # sampled pixels of the last timed frame
+DUMP_RAY_STEPS = range(-4, 5)  # voxels along the pixel's ray, about its surface point
+
+
+def dump_outputs(a, engines, depth, frame_id, images=None, mesh_tris=None):
+    """--dump-outputs: what the last timed step left for a caller, as float32 / float64 .npy files.
+
+    The volume itself is too large to write (2^block_bits blocks x 6 KB), so the voxels are read at
+    a fixed, seeded sample of voxel coordinates, independent of where the hash table or the pool put
+    them: DUMP_PIXELS pixels with a depth reading of the last timed frame (a seeded permutation of
+    the image), each back-projected with that frame's pose, and the voxels DUMP_RAY_STEPS voxel
+    lengths along its ray about that point -- the truncation band the step just updated. engines:
+    the engine, or the shard engines of one volume (a voxel comes from the shard that holds its
+    block). A coordinate in no allocated block reads tsdf 1, prob 0, rgbw 0 (tsdf_hash_retrieve)."""
+    import numpy as np
+
+    from tsdf_amd import synth
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    d = depth.cpu().numpy() if hasattr(depth, "cpu") else np.asarray(depth)
+    cam = synth.camera(a.width, a.height, synth.TUM_FR1 if a.width <= 640 else synth.L515_FULL)
+    (R_wc, p), _ = synth.pose(frame_id)
+    order = np.random.Generator(np.random.PCG64(DUMP_SEED)).permutation(a.width * a.height)
+    pix = order[d.reshape(-1)[order] > 0][:DUMP_PIXELS]
+    u, v = (pix % a.width).astype(np.float64), (pix // a.width).astype(np.float64)
+    ray = np.stack([(u - cam.cx) / cam.fx, (v - cam.cy) / cam.fy, np.ones_like(u)], -1) @ R_wc.T
+    z = d.reshape(-1)[pix].astype(np.float64)
+    step = a.voxel / np.linalg.norm(ray, axis=1)
+    pts = np.concatenate([p + ((z + k * step)[:, None] * ray) for k in DUMP_RAY_STEPS])
+    vox = np.unique(np.floor(pts / a.voxel).astype(np.int16), axis=0)  # sorted: the files' row order
+    got = None
+    for e in engines:
+        r = e.hash_retrieve(vox)
+        if got is None:
+            got = r
+        else:
+            own = r["block_idx"] >= 0
+            for k in ("tsdf", "prob", "rgbw"):
+                got[k][own] = r[k][own]
+    stats = [e.stats() for e in engines]
+    out = {"voxel_xyz": vox.astype(np.float32), "tsdf": got["tsdf"], "prob": got["prob"],
+           "rgbw": got["rgbw"].astype(np.float32),
+           "counts": np.array([sum(s[k] for s in stats) for k in
+                               ("active_blocks", "last_num_visible", "last_num_updated")], np.float64)}
+    for name, img in (images or {}).items():
+        if img is not None:
+            out[name] = img.cpu().numpy().astype(np.float32)
+    if mesh_tris:
+        out["mesh_triangles"] = np.array(mesh_tris, np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
 
 
 def frame_broadcast_ms(a, dist, _unused, dev, reps=20):
@@ -794,6 +876,8 @@ def rehearsal(a, cam, K, dev):
         "max_shard_device_us_per_frame": round(max(dev_total), 3),
         "avg_visible_blocks_per_shard": [round(p["sum_visible"] / n, 1) for p in profs],
     }
+    if a.dump_outputs:
+        dump_outputs(a, grp.engines, fr["depth"][nframes - 1], nframes - 1)
     grp.close()
     print(json.dumps(out), flush=True)
 

@@ -9,7 +9,7 @@
 #   profile-driver    kernel trace + FETCH_SIZE / WRITE_SIZE PMC passes of the driver command
 #                     (scripts/profile_integrate.sh; summary + pmc_entry.json under <tag>/prof_driver)
 #   profile-c3|c4|c5|c5graph|c2  the same for those bench lines (default steps) -> <tag>/prof_<name>
-#   default           bench.py (300 timed frames, CPU baseline)
+#   default           bench.py --full (300 timed frames, CPU baseline, C++ loop)
 #   c5 | c5graph | c4 | c2 | graph   bench.py --loop c5 [--graph] / 1280x720 / --depth-only / --graph
 #   c5tests           the raycast / render / C5 GPU tests
 #   host-pinned|host-pageable  bench.py --host-frames (C3 frames from host memory through TSDF_MEM_HOST)
@@ -56,7 +56,7 @@ for st in "$@"; do
                        profile-c5graph) A="--loop c5 --graph";; profile-c2) A="--depth-only";; esac
            bash scripts/profile_integrate.sh $OUT/prof_${st#profile-} $A || fail $st $OUT/prof_${st#profile-}/trace_bench.log
            tail -14 $OUT/prof_${st#profile-}/summary.txt ;;
-    default) timeout -k 10 300 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || fail $st $OUT/bench_default.err
+    default) timeout -k 10 300 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || fail $st $OUT/bench_default.err
            line $OUT/bench_default.json ;;
     c5) timeout -k 10 300 python3 bench.py --no-cpu --loop c5 > $OUT/bench_c5.json 2> $OUT/bench_c5.err || fail $st $OUT/bench_c5.err
            line $OUT/bench_c5.json ;;
@@ -69,7 +69,7 @@ for st in "$@"; do
     c2) timeout -k 10 300 python3 bench.py --no-cpu --depth-only > $OUT/bench_c2.json 2> $OUT/bench_c2.err || fail $st $OUT/bench_c2.err
            line $OUT/bench_c2.json ;;
     host-pinned|host-pageable) k=${st#host-}
-           timeout -k 10 300 python3 bench.py --no-cpu --host-frames $k > $OUT/bench_host_$k.json 2> $OUT/bench_host_$k.err || fail $st $OUT/bench_host_$k.err
+           timeout -k 10 300 python3 bench.py --full --no-cpu --host-frames $k > $OUT/bench_host_$k.json 2> $OUT/bench_host_$k.err || fail $st $OUT/bench_host_$k.err
            line $OUT/bench_host_$k.json; grep -o '"host_frames": {[^}]*}' $OUT/bench_host_$k.json ;;
     c5tests) timeout -k 10 600 $PYT tests/test_gpu_c5.py tests/test_gpu_render.py tests/test_gpu_parity.py tests/test_gpu_golden.py tests/test_gpu_graph.py -m gpu > $OUT/pytest_c5.log 2>&1 || fail $st $OUT/pytest_c5.log
            tail -1 $OUT/pytest_c5.log ;;

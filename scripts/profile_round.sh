@@ -5,7 +5,7 @@ set -euo pipefail
 TAG=${1:?tag}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-timeout -k 10 200 python3 bench.py > "$OUT/bench_plain.log" 2>&1
+timeout -k 10 200 python3 bench.py --full > "$OUT/bench_plain.log" 2>&1
 bash scripts/profile_integrate.sh "$OUT"
 bash scripts/profile_sq.sh "$OUT" 60
 python3 scripts/summarize_prof.py "$OUT" > "$OUT/summary.txt"
