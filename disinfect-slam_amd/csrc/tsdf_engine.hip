@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <string>
 #include <deque>
+#include <limits>
 #include <vector>
 
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -224,6 +225,16 @@ struct tsdf_engine {
   int mesh_grid = 0;            // k_mesh workgroups: min(kMeshGrid, pool blocks)
   float* m_out = nullptr;
   int64_t m_out_cap = 0;  // triangles
+  // indexed mesh scratch (tsdf_extract_mesh_indexed): allocated by its first call, grow-only
+  unsigned long long* mi_emask = nullptr;  // mi_cap selected blocks x kEdgeWords
+  uint16_t* mi_epre = nullptr;             // x kEdgePre
+  int32_t* mi_vcounts = nullptr;
+  int32_t* mi_voffsets = nullptr;
+  int64_t* mi_vtotal = nullptr;
+  int32_t* mi_selmap = nullptr;            // pool blocks
+  int32_t mi_cap = 0;
+  uint8_t* mi_out = nullptr;               // staging of a host output
+  size_t mi_out_bytes = 0;
   int16_t* t_keys = nullptr;
   VisRec* t_recs = nullptr;
   int32_t* t_count = nullptr;
@@ -290,7 +301,7 @@ void free_all(tsdf_engine* e) {
                   D.vis,     D.band,    D.cand,     D.arrive, D.swdirty, D.fresh_vis, D.pend, D.pixA, D.pixC,     D.visbits,    D.wgcnt, D.dbg,
                   e->s_rgb,  e->s_depth, e->s_ht,    e->s_lt,   e->rc_rgba,   e->rc_norm,
                   e->vg_cell, e->vg_flags, e->vg_bits, e->g_visbits, e->g_wgcnt, e->g_sel, e->g_count,
-                  e->q_sel,  e->q_count, e->q_out, e->m_counts, e->m_offsets, e->m_total, e->m_nbr, e->m_out,   e->t_keys, e->t_recs,    e->t_count,
+                  e->q_sel,  e->q_count, e->q_out, e->m_counts, e->m_offsets, e->m_total, e->m_nbr, e->m_out,   e->mi_emask, e->mi_epre, e->mi_vcounts, e->mi_voffsets, e->mi_vtotal, e->mi_selmap, e->mi_out, e->t_keys, e->t_recs,    e->t_count,
                   e->t_i32,  e->t_u32,   e->t_f0,    e->t_f1,   e->t_s4};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -2613,6 +2624,130 @@ int tsdf_extract_mesh_owned(tsdf_engine* e, const float* bounds, float missing_t
   TraceRange trace_("tsdf_extract_mesh_owned");
   return extract_mesh_impl(e, bounds, missing_tsdf, min_weight, shard_index, shard_count, triangles, capacity,
                            num_triangles, mem_kind);
+}
+
+int tsdf_extract_mesh_indexed(tsdf_engine* e, const float* bounds, float missing_tsdf, int min_weight,
+                              const tsdf_mesh_out* out, int64_t* num_vertices, int64_t* num_triangles) {
+  TraceRange trace_("tsdf_extract_mesh_indexed");
+  if (!e || !num_vertices || !num_triangles ||
+      (out && (!out->positions || !out->indices || out->vertex_capacity < 0 || out->triangle_capacity < 0 ||
+               (reinterpret_cast<uintptr_t>(out->rgba) & 3) != 0 ||
+               (out->mem_kind != TSDF_MEM_HOST && out->mem_kind != TSDF_MEM_DEVICE)))) {
+    set_error("tsdf_extract_mesh_indexed: invalid argument (positions and indices are required with out; rgba 4-byte aligned)");
+    return TSDF_ERR_INVALID_ARG;
+  }
+  if (e->cfg.shard_count > 1) {
+    set_error("tsdf_extract_mesh_indexed: not available on a shard engine (shard_count > 1)");
+    return TSDF_ERR_INVALID_ARG;
+  }
+  HIP_OK(hipSetDevice(e->device));
+  ENTER(e);
+  short4 lo = make_short4(0, 0, 0, 0), hi = make_short4(0, 0, 0, 0);
+  if (bounds) {  // the Query block selection (voxel_tsdf.cuh:21-26, voxel_tsdf.cu:429)
+    const float scale = (float)(1. / (double)e->cfg.voxel_size);
+    lo = make_short4(h_f2s(bounds[0] * scale), h_f2s(bounds[2] * scale), h_f2s(bounds[4] * scale), 0);
+    hi = make_short4(h_f2s(bounds[1] * scale), h_f2s(bounds[3] * scale), h_f2s(bounds[5] * scale), 0);
+  }
+  hipStream_t s = e->stream;
+  const int nb = e->D.nblocks;
+  if (!e->mi_selmap) {
+    HIP_OK(dmalloc(&e->mi_selmap, (size_t)nb));
+    HIP_OK(dmalloc(&e->mi_vtotal, 1));
+  }
+  const MeshParams M{e->cfg.voxel_size, missing_tsdf, min_weight, 0, 1};
+  const bool dev_out = out && out->mem_kind == TSDF_MEM_DEVICE;
+  const int64_t vmax = std::numeric_limits<int32_t>::max();
+  MeshIndexedOut O{};
+  if (out) {
+    O = MeshIndexedOut{out->positions, out->rgba, out->prob, out->keys, out->indices,
+                       std::min(out->vertex_capacity, vmax), out->triangle_capacity};
+  }
+  auto scratch = [&] {
+    return MeshIndexed{e->m_nbr,      e->m_counts,   e->m_offsets,  e->m_total,   e->mi_emask, e->mi_epre,
+                       e->mi_vcounts, e->mi_voffsets, e->mi_vtotal, e->mi_selmap, e->mi_cap};
+  };
+  auto emit = [&](const MeshIndexedOut& o) {
+    hipLaunchKernelGGL(k_mesh_verts, dim3(e->mesh_grid), dim3(256), 0, s, e->D, e->q_sel, e->q_count, M, scratch(), o);
+    hipLaunchKernelGGL(k_mesh_index, dim3(e->mesh_grid), dim3(256), 0, s, e->D, e->q_sel, e->q_count, M, scratch(), o);
+  };
+  // selection, the two count passes, their scans and (device output) the vertex and index passes
+  // enqueued back to back; the host reads the selection size and the two totals once at the end. A
+  // selection larger than the scratch holds makes every pass return at once: the scratch grows and
+  // the passes run again (the first call, and after the volume has grown).
+  int32_t nsel = 0;
+  int64_t nv = 0, nt = 0;
+  for (;;) {
+    hipLaunchKernelGGL(k_query_count, dim3(kOccWords / 256), dim3(256), 0, s, e->D, bounds ? 1 : 0, lo, hi);
+    hipLaunchKernelGGL(k_vis_emit, dim3(kOccWords / 256), dim3(256), 0, s, e->D, e->q_sel, e->q_count);
+    LAUNCH_OK("indexed mesh select");
+    if (e->mi_cap > 0) {
+      hipLaunchKernelGGL(k_mesh<false>, dim3(e->mesh_grid), dim3(256), 0, s, e->D, e->q_sel, e->q_count, M,
+                         e->m_counts, (const int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, e->m_nbr,
+                         (float*)nullptr);
+      hipLaunchKernelGGL(k_mesh_edges, dim3(e->mesh_grid), dim3(256), 0, s, e->D, e->q_sel, e->q_count, M, scratch());
+      hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, e->m_counts, e->q_count, e->m_offsets, e->m_total);
+      hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, e->mi_vcounts, e->q_count, e->mi_voffsets,
+                         e->mi_vtotal);
+      LAUNCH_OK("indexed mesh count");
+      if (dev_out) {
+        emit(O);
+        LAUNCH_OK("indexed mesh emit");
+      }
+      HIP_OK(hipMemcpyAsync(&nv, e->mi_vtotal, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(&nt, e->m_total, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipMemcpyAsync(&nsel, e->q_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (nsel <= e->mi_cap) break;
+    for (void* p : {(void*)e->mi_emask, (void*)e->mi_epre, (void*)e->mi_vcounts, (void*)e->mi_voffsets})
+      if (p) (void)hipFree(p);
+    e->mi_emask = nullptr, e->mi_epre = nullptr, e->mi_vcounts = nullptr, e->mi_voffsets = nullptr;
+    e->mi_cap = 0;
+    const int32_t cap = (int32_t)std::min<int64_t>(nb, std::max<int64_t>((int64_t)nsel + nsel / 4, 1024));
+    HIP_OK(dmalloc(&e->mi_emask, (size_t)cap * kEdgeWords));
+    HIP_OK(dmalloc(&e->mi_epre, (size_t)cap * kEdgePre));
+    HIP_OK(dmalloc(&e->mi_vcounts, (size_t)cap));
+    HIP_OK(dmalloc(&e->mi_voffsets, (size_t)cap));
+    e->mi_cap = cap;
+  }
+  if (nsel == 0) nv = nt = 0;
+  *num_vertices = nv;
+  *num_triangles = nt;
+  if (!out || (nv == 0 && nt == 0)) return TSDF_OK;
+  if (nv > vmax || out->vertex_capacity < nv || out->triangle_capacity < nt) {  // (nothing was written)
+    set_error("tsdf_extract_mesh_indexed: capacity too small");
+    return TSDF_ERR_CAPACITY;
+  }
+  if (dev_out) return TSDF_OK;
+  // host output: the passes write a staging buffer (sections 16-byte aligned), copied out per array
+  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_pos = 0, o_idx = o_pos + up((size_t)nv * 12), o_rgba = o_idx + up((size_t)nt * 12),
+               o_prob = o_rgba + up((size_t)nv * 4), o_keys = o_prob + up((size_t)nv * 4),
+               bytes = o_keys + up((size_t)nv * 16);
+  if (e->mi_out_bytes < bytes) {
+    if (e->mi_out) (void)hipFree(e->mi_out);
+    e->mi_out = nullptr;
+    e->mi_out_bytes = 0;
+    HIP_OK(dmalloc(&e->mi_out, bytes));
+    e->mi_out_bytes = bytes;
+  }
+  uint8_t* b = e->mi_out;
+  const MeshIndexedOut S{reinterpret_cast<float*>(b + o_pos),
+                         out->rgba ? b + o_rgba : nullptr,
+                         out->prob ? reinterpret_cast<float*>(b + o_prob) : nullptr,
+                         out->keys ? reinterpret_cast<int32_t*>(b + o_keys) : nullptr,
+                         reinterpret_cast<int32_t*>(b + o_idx),
+                         nv,
+                         nt};
+  emit(S);
+  LAUNCH_OK("indexed mesh emit");
+  HIP_OK(hipMemcpyAsync(out->positions, S.positions, (size_t)nv * 12, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(out->indices, S.indices, (size_t)nt * 12, hipMemcpyDeviceToHost, s));
+  if (out->rgba) HIP_OK(hipMemcpyAsync(out->rgba, S.rgba, (size_t)nv * 4, hipMemcpyDeviceToHost, s));
+  if (out->prob) HIP_OK(hipMemcpyAsync(out->prob, S.prob, (size_t)nv * 4, hipMemcpyDeviceToHost, s));
+  if (out->keys) HIP_OK(hipMemcpyAsync(out->keys, S.keys, (size_t)nv * 16, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return TSDF_OK;
 }
 
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* o, int clear_status) {

@@ -262,6 +262,36 @@ template <bool Emit>
 __global__ void k_mesh(EngineDev D, const VisRec* sel, const int32_t* nsel, MeshParams M, int32_t* counts,
                        const int32_t* offsets, const int64_t* total, int64_t capacity, int32_t* nbr, float* out);
 __global__ void k_scan_counts(const int32_t* counts, const int32_t* nsel, int32_t* offsets, int64_t* total);
+// indexed mesh (tsdf_extract_mesh_indexed; the passes are described in tsdf_mesh.hip): the engine's
+// scratch for `cap` selected blocks, and the caller's (or the staging) output arrays
+constexpr int kEdgeWords = 27;            // 1728 = 3 * 512 + 3 * 64 possible edges of a block, 64 per word
+constexpr int kEdgePre = kEdgeWords + 1;  // vertices before each word, then the block's count
+struct MeshIndexed {
+  const int32_t* nbr;         // k_mesh<false>'s neighbour pool indices, triangle counts, offsets, total
+  const int32_t* tcounts;
+  const int32_t* toffsets;
+  const int64_t* ttotal;
+  unsigned long long* emask;  // cap x kEdgeWords: the block's crossed, owned edges
+  uint16_t* epre;             // cap x kEdgePre
+  int32_t* vcounts;           // cap: vertices per block, and their scan
+  int32_t* voffsets;
+  int64_t* vtotal;
+  int32_t* selmap;            // pool blocks: selection index of a selected block (stale otherwise)
+  int32_t cap;
+};
+struct MeshIndexedOut {
+  float* positions;
+  uint8_t* rgba;     // null: skipped
+  float* prob;       // null: skipped
+  int32_t* keys;     // null: skipped
+  int32_t* indices;
+  int64_t vcap, tcap;  // nothing is written when either total exceeds its capacity
+};
+__global__ void k_mesh_edges(EngineDev D, const VisRec* sel, const int32_t* nsel, MeshParams M, MeshIndexed X);
+__global__ void k_mesh_verts(EngineDev D, const VisRec* sel, const int32_t* nsel, MeshParams M, MeshIndexed X,
+                             MeshIndexedOut O);
+__global__ void k_mesh_index(EngineDev D, const VisRec* sel, const int32_t* nsel, MeshParams M, MeshIndexed X,
+                             MeshIndexedOut O);
 __global__ void k_raycast(EngineDev D, FrameParams P, float step_size, ViewGrid V, uchar4* rgba,
                           uchar4* normal);
 // frame n's raycast (R, V: its view grid, built before) + frame n + 1's ingest (k_ingest_dda<1024>) in

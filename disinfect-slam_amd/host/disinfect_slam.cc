@@ -39,4 +39,6 @@ std::vector<VoxelSpatialTSDF> DISINFSystem::query_tsdf(const BoundingCube<float>
   return TSDF_->Query(volumn);
 }
 
+TriMesh DISINFSystem::query_mesh(const BoundingCube<float>& volumn) { return TSDF_->QueryMesh(volumn); }
+
 }  // namespace disinfect

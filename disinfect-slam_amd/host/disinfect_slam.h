@@ -27,6 +27,9 @@ class DISINFSystem {
   void register_camera_pose(int64_t timestamp, const SE3<float>& cam_T_world);
   SE3<float> query_camera_pose(int64_t timestamp);                              // :108-111
   std::vector<VoxelSpatialTSDF> query_tsdf(const BoundingCube<float>& volumn);  // :113-116
+  // the surface in `volumn` as an indexed mesh with colour and high-touch probability: what tsdfCb
+  // builds from query_tsdf's voxels on the CPU (ros_offline.cc:286-313), extracted on the GPU
+  TriMesh query_mesh(const BoundingCube<float>& volumn);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

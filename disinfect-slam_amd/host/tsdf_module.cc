@@ -75,6 +75,11 @@ std::vector<VoxelSpatialTSDF> TSDFSystem::Query(const BoundingCube<float>& volum
   return tsdf_.GatherVoxels(volumn);
 }
 
+TriMesh TSDFSystem::QueryMesh(const BoundingCube<float>& volumn) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  return tsdf_.ExtractMesh(&volumn);
+}
+
 void TSDFSystem::Render(const CameraParams& virtual_cam, const SE3<float> cam_T_world, Mat* img_normal) {
   std::lock_guard<std::mutex> lock(mtx_read_);
   tsdf_.RayCast(max_depth_, virtual_cam, cam_T_world, nullptr, img_normal);

@@ -55,6 +55,7 @@ class TSDFSystem {
   void IntegrateRaw(const SE3<float>& posecam_T_world, const Mat& img_rgb, const Mat& img_depth_raw,
                     const Mat& mask, float depth_factor);
   std::vector<VoxelSpatialTSDF> Query(const BoundingCube<float>& volumn);
+  TriMesh QueryMesh(const BoundingCube<float>& volumn);  // TSDFGrid::ExtractMesh, under Query's lock
   void Render(const CameraParams& virtual_cam, const SE3<float> cam_T_world, Mat* img_normal);
 
   // block until every queued frame has been integrated (not in the reference; used by tests)

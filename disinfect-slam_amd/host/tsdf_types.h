@@ -205,4 +205,13 @@ struct VoxelSpatialTSDF {  // 16 B, identical layout to tsdf_voxel of the C ABI
   float tsdf;
 };
 
+// The indexed mesh of tsdf_extract_mesh_indexed: what tsdfCb publishes from Meshing::TriMesh verts +
+// tris (examples/ros_camera_driver/ros_offline.cc:286-313), plus the volume's semantics per vertex.
+struct TriMesh {
+  std::vector<float> verts;    // 3 per vertex
+  std::vector<int32_t> tris;   // 3 vertex indices per triangle
+  std::vector<uint8_t> rgba;   // 4 per vertex: r, g, b, fusion weight
+  std::vector<float> prob;     // 1 per vertex: high-touch probability
+};
+
 }  // namespace disinfect

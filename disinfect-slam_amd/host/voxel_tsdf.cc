@@ -127,6 +127,35 @@ std::vector<VoxelSpatialTSDF> TSDFGrid::GatherVoxels(const BoundingCube<float>& 
   return Query(b);
 }
 
+TriMesh TSDFGrid::ExtractMesh(const BoundingCube<float>* v, float missing_tsdf, int min_weight) {
+  if (group_) throw std::runtime_error("TSDFGrid::ExtractMesh: not available on a sharded volume");
+  float b[6];
+  if (v) {
+    const float vb[6] = {v->xmin, v->xmax, v->ymin, v->ymax, v->zmin, v->zmax};
+    for (int i = 0; i < 6; ++i) b[i] = vb[i];
+  }
+  int64_t nv = 0, nt = 0;
+  check_tsdf(tsdf_extract_mesh_indexed(engine_, v ? b : nullptr, missing_tsdf, min_weight, nullptr, &nv, &nt),
+             "tsdf_extract_mesh_indexed");
+  TriMesh m;
+  m.verts.resize((size_t)nv * 3);
+  m.tris.resize((size_t)nt * 3);
+  m.rgba.resize((size_t)nv * 4);
+  m.prob.resize((size_t)nv);
+  if (nv == 0 && nt == 0) return m;
+  tsdf_mesh_out out{};
+  out.positions = m.verts.data();
+  out.rgba = m.rgba.data();
+  out.prob = m.prob.data();
+  out.indices = m.tris.data();
+  out.vertex_capacity = nv;
+  out.triangle_capacity = nt;
+  out.mem_kind = TSDF_MEM_HOST;
+  check_tsdf(tsdf_extract_mesh_indexed(engine_, v ? b : nullptr, missing_tsdf, min_weight, &out, &nv, &nt),
+             "tsdf_extract_mesh_indexed");
+  return m;
+}
+
 tsdf_stats TSDFGrid::Stats(bool clear_status) {
   tsdf_stats s;
   if (group_)

@@ -43,6 +43,12 @@ class TSDFGrid {
   std::vector<VoxelSpatialTSDF> GatherValid();                                  // :399-425
   std::vector<VoxelSpatialTSDF> GatherVoxels(const BoundingCube<float>& volumn);  // :427-454
 
+  // marching-cubes mesh with shared vertices, colour and high-touch probability
+  // (tsdf_extract_mesh_indexed; volumn null = every allocated block). Not available on a sharded
+  // volume: throws std::runtime_error.
+  TriMesh ExtractMesh(const BoundingCube<float>* volumn = nullptr, float missing_tsdf = 0.99f,
+                      int min_weight = 0);
+
   tsdf_stats Stats(bool clear_status = false);
   tsdf_engine* engine() { return engine_; }  // (NULL for a sharded volume)
   tsdf_group* group() { return group_; }      // (NULL for one engine)

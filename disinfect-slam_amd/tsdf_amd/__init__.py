@@ -340,6 +340,8 @@ class Engine:
         # engine's NEXT call writes: referenced until then (torch's allocator must not reuse them), and
         # torch's current stream is ordered after that call -- see _after_call
         self._pending = None
+        # extract_mesh_indexed(device=True): vertex / triangle capacities of its first attempt
+        self._mesh_caps = (1 << 16, 1 << 17)
 
     def _after_call(self, prev):
         """Engine call wrapper epilogue: the call launched the deferred raycast `prev` was waiting for
@@ -783,6 +785,57 @@ class Engine:
         if n.value:
             _lib.check(fn(_ptr(tris), n.value, n, TSDF_MEM_HOST), "tsdf_extract_mesh")
         return tris
+
+    def extract_mesh_indexed(self, bounds=None, missing_tsdf: float = 0.99, min_weight: int = 0,
+                             device: bool = False) -> dict:
+        """The mesh of extract_mesh with shared vertices and the volume's semantics
+        (tsdf_extract_mesh_indexed): a dict of positions (n, 3) f32, rgba (n, 4) u8 (r, g, b, weight),
+        prob (n,) f32 (high-touch probability), keys (n, 4) i32 (the vertex's grid edge: global voxel
+        coordinate of its lower endpoint, axis) and indices (m, 3) i32; triangle i is triangle i of
+        extract_mesh. numpy arrays, or with device=True torch tensors on this engine's GPU written by
+        one call (ordered against torch's stream like extract_mesh(out=...))."""
+        L = _lib.load()
+        b = None if bounds is None else np.ascontiguousarray(
+            bounds.as_array() if isinstance(bounds, BoundingCube) else bounds, dtype=np.float32)
+        nv, nt = C.c_int64(), C.c_int64()
+
+        def call(m):
+            return L.tsdf_extract_mesh_indexed(self._h, _ptr(b), missing_tsdf, min_weight,
+                                               None if m is None else C.byref(m), C.byref(nv), C.byref(nt))
+
+        def struct(a, vcap, tcap, kind):
+            return _lib.MeshOut(_ptr(a["positions"]), _ptr(a["rgba"]), _ptr(a["prob"]), _ptr(a["keys"]),
+                                _ptr(a["indices"]), vcap, tcap, kind)
+
+        if device:
+            import torch
+            dev = f"cuda:{self.device}"
+            vcap, tcap = self._mesh_caps
+            for attempt in range(2):  # once more with the returned counts when the guess was too small
+                a = dict(positions=torch.empty((vcap, 3), dtype=torch.float32, device=dev),
+                         rgba=torch.empty((vcap, 4), dtype=torch.uint8, device=dev),
+                         prob=torch.empty((vcap,), dtype=torch.float32, device=dev),
+                         keys=torch.empty((vcap, 4), dtype=torch.int32, device=dev),
+                         indices=torch.empty((tcap, 3), dtype=torch.int32, device=dev))
+                self._wait_torch(*a.values())
+                rc = call(struct(a, vcap, tcap, TSDF_MEM_DEVICE))
+                self._signal_torch(*a.values())
+                if rc != _lib.TSDF_ERR_CAPACITY or attempt == 1:
+                    break
+                vcap, tcap = nv.value, nt.value
+            _lib.check(rc, "tsdf_extract_mesh_indexed")
+            # the next call's first guess: this mesh and a quarter
+            self._mesh_caps = (nv.value + nv.value // 4 + 1024, nt.value + nt.value // 4 + 1024)
+            n, m = nv.value, nt.value
+            return {k: (v[:m] if k == "indices" else v[:n]) for k, v in a.items()}
+        _lib.check(call(None), "tsdf_extract_mesh_indexed")
+        n, m = nv.value, nt.value
+        a = dict(positions=np.zeros((n, 3), np.float32), rgba=np.zeros((n, 4), np.uint8),
+                 prob=np.zeros(n, np.float32), keys=np.zeros((n, 4), np.int32),
+                 indices=np.zeros((m, 3), np.int32))
+        if n or m:
+            _lib.check(call(struct(a, n, m, TSDF_MEM_HOST)), "tsdf_extract_mesh_indexed")
+        return a
 
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()

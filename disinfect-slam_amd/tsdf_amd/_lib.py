@@ -97,6 +97,19 @@ class Profile(C.Structure):
     ]
 
 
+class MeshOut(C.Structure):
+    _fields_ = [
+        ("positions", C.c_void_p),
+        ("rgba", C.c_void_p),
+        ("prob", C.c_void_p),
+        ("keys", C.c_void_p),
+        ("indices", C.c_void_p),
+        ("vertex_capacity", C.c_int64),
+        ("triangle_capacity", C.c_int64),
+        ("mem_kind", C.c_int),
+    ]
+
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -116,6 +129,7 @@ EXPORTS = [
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_integrate", "tsdf_group_flush",
     "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats", "tsdf_group_query", "tsdf_group_raycast",
     "tsdf_group_stream_signal",
+    "tsdf_extract_mesh_indexed",
 ]
 
 _lib = None
@@ -190,6 +204,7 @@ def load(path: str | None = None):
     L.tsdf_pack_blocks.argtypes = [P, P, P, i64, C.POINTER(i64), i]
     L.tsdf_query.argtypes = [P, P, P, i64, C.POINTER(i64)]
     L.tsdf_extract_mesh.argtypes = [P, P, f, i, P, i64, C.POINTER(i64), i]
+    L.tsdf_extract_mesh_indexed.argtypes = [P, P, f, i, C.POINTER(MeshOut), C.POINTER(i64), C.POINTER(i64)]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -235,7 +250,8 @@ def load(path: str | None = None):
                  "tsdf_graph_create_batch",
                  "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_integrate",
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
-                 "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal"):
+                 "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
+                 "tsdf_extract_mesh_indexed"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

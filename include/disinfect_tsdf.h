@@ -406,6 +406,41 @@ int tsdf_extract_mesh_owned(tsdf_engine* e, const float* bounds, float missing_t
 int tsdf_extract_mesh(tsdf_engine* e, const float* bounds, float missing_tsdf, int min_weight,
                       float* triangles, int64_t capacity, int64_t* num_triangles, int mem_kind);
 
+/* The same mesh with shared vertices and the volume's semantics attached: what the reference
+ * publishes as shape_msgs::Mesh from Meshing::TriMesh verts + tris in tsdfCb
+ * (examples/ros_camera_driver/ros_offline.cc:286-313), plus colour and high-touch probability.
+ * Block selection, sampling rule, meshed cells, triangle order and winding are those of
+ * tsdf_extract_mesh: triangle i is triangle i of the soup, positions[indices[...]] equals it bit for
+ * bit.
+ * Vertices: one per crossed grid edge (one sample < 0, the other not). Endpoint a is the lower one
+ * along the edge's axis, b = a + 1 on it. keys = global voxel coordinate of a (8 * block + local),
+ * then the axis 0 / 1 / 2: the vertex's identity across extractions. Two crossed edges with one
+ * position (tt == 0 at a shared corner) stay two vertices.
+ *   position: tt = va / (va - vb); axis coordinate pa + tt * (pb - pa) (the soup's expression);
+ *   an endpoint is valid when its tsdf, not missing_tsdf, was its sample. Both valid:
+ *   prob = qa + tt * (qb - qa), each rgbw byte (uint8_t)(int)(fa + tt * (fb - fa) + 0.5f), all
+ *   fp32 op by op; one valid: that endpoint's prob and rgbw unchanged.
+ * Vertex order: selected blocks in entry order; an edge belongs to the block of its lower endpoint
+ * when that block is selected, else to the block of its upper endpoint (the lower endpoint then has
+ * local coordinate -1 on the axis); inside a block by the lower endpoint's local (z, y, x), then
+ * the axis. The order does not depend on launch sizes or scheduling.
+ * out == NULL: the two counts only. TSDF_MEM_HOST: the two-call pattern. TSDF_MEM_DEVICE: one call
+ * may do everything; both counts are always set, and when either capacity is too small (or there
+ * are more than INT32_MAX vertices) nothing is written and TSDF_ERR_CAPACITY is returned.
+ * positions and indices are required with out. Completes a pending pipelined frame first. Not
+ * available on a shard engine (shard_count > 1): TSDF_ERR_INVALID_ARG. */
+typedef struct tsdf_mesh_out {
+  float* positions;  /* 3 per vertex */
+  uint8_t* rgba;     /* 4 per vertex: r, g, b, weight (4-byte aligned); NULL = skip */
+  float* prob;       /* 1 per vertex: high-touch probability; NULL = skip */
+  int32_t* keys;     /* 4 per vertex: gx, gy, gz, axis; NULL = skip */
+  int32_t* indices;  /* 3 per triangle */
+  int64_t vertex_capacity, triangle_capacity;
+  int mem_kind;      /* TSDF_MEM_HOST or TSDF_MEM_DEVICE (all pointers alike) */
+} tsdf_mesh_out;
+int tsdf_extract_mesh_indexed(tsdf_engine* e, const float* bounds, float missing_tsdf, int min_weight,
+                              const tsdf_mesh_out* out, int64_t* num_vertices, int64_t* num_triangles);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
