@@ -294,6 +294,40 @@ __global__ void k_mesh_index(EngineDev D, const VisRec* sel, const int32_t* nsel
                              MeshIndexedOut O);
 __global__ void k_raycast(EngineDev D, FrameParams P, float step_size, ViewGrid V, uchar4* rgba,
                           uchar4* normal);
+// pose tracking (tsdf_track.hip; DESIGN.md "Pose tracking")
+// the float maps of tsdf_raycast_surface, H x W each: point and normal 3 floats per pixel, rgbw the
+// voxel's packed r, g, b, weight; depth / prob / rgbw null: skipped
+struct SurfaceOut {
+  float* point;
+  float* normal;
+  float* depth;
+  float* prob;
+  uint32_t* rgbw;
+};
+// k_raycast's sibling: the same grid, tiles and march, the hits as SurfaceOut maps
+__global__ void k_raycast_surface(EngineDev D, FrameParams P, float step_size, ViewGrid V, SurfaceOut S);
+// tsdf_track's model normals from the surface points (P: the model camera; grid of 16x16 tiles)
+constexpr float kTrackMinCos = 0.3f;  // least cosine between such a normal and the viewing ray
+__global__ void k_surface_normals(FrameParams P, const float* point, const float* normal, float* out);
+// One point-to-plane linearisation (tsdf_icp_linearize): F the depth frame's camera at the estimate
+// (intrinsics_inv, world_T_cam), M the model maps' camera (intrinsics, cam_T_world). Sample s of the
+// nsx * nsy sampled pixels is pixel (stride * (s % nsx), stride * (s / nsx)); thread t of workgroup g
+// of k_icp_partial takes sample 256 g + t.
+constexpr int kIcpSums = 29;  // 21 of J J^T's upper triangle, 6 of J r, r^2, count
+struct IcpParams {
+  FrameParams F, M;
+  const float* depth;
+  const float* point;
+  const float* normal;
+  int stride, nsx, nsamples;
+  float max_dist2;
+};
+__global__ void k_icp_partial(IcpParams I, double* part);
+// the partials of the nwg workgroups added in a fixed order (one workgroup of 1024: kIcpChunks runs of
+// consecutive workgroups, one thread per run and sum, then the runs in index order)
+constexpr int kIcpChunks = 32;
+static_assert(kIcpChunks * kIcpSums <= 1024, "k_icp_final's workgroup");
+__global__ void k_icp_final(const double* part, int nwg, double* out);
 // frame n's raycast (R, V: its view grid, built before) + frame n + 1's ingest (k_ingest_dda<1024>) in
 // one launch: nray raycast workgroups (rgx tiles per row) first, then kVisWorkgroups + tiles (tsdf_alloc.hip)
 __global__ void k_render_ingest(EngineDev D, FrameParams R, float step_size, ViewGrid V, uchar4* rgba,

@@ -1,5 +1,6 @@
 // tsdf_raycast.h -- the raycast march (ray_cast_kernel, utils/tsdf/voxel_tsdf.cu:232-307): used by
-// k_raycast (tsdf_extract.hip) and by the fused render + ingest launch k_render_ingest (tsdf_alloc.hip).
+// k_raycast (tsdf_extract.hip), by the fused render + ingest launch k_render_ingest (tsdf_alloc.hip)
+// and, with float surface maps as its output, by k_raycast_surface (tsdf_track.hip).
 #pragma once
 
 #include "tsdf_block.h"
@@ -92,8 +93,8 @@ __device__ __forceinline__ float ray_tsdf(const EngineDev& D, const RayView& R, 
 
 // The hit of ray_cast_kernel (voxel_tsdf.cu:259-300) at position hp: binary search between
 // hp - step and hp, the voxel's colour / probability and the central-difference normal.
-__device__ __forceinline__ void ray_shade(const EngineDev& D, const RayView& R, RayCache& c, f3 hp, f3 sg,
-                                       f3 dw, uchar4* __restrict__ rgba, uchar4* __restrict__ normal, int idx) {
+// (the binary search alone: the point whose nearest voxel the hit is shaded from)
+__device__ __forceinline__ f3 ray_search(const EngineDev& D, const RayView& R, RayCache& c, f3 hp, f3 sg) {
   f3 p1 = {hp.x - sg.x, hp.y - sg.y, hp.z - sg.z};
   f3 p2 = hp;
   f3 mid = {(p1.x + p2.x) / 2, (p1.y + p2.y) / 2, (p1.z + p2.z) / 2};
@@ -108,6 +109,11 @@ __device__ __forceinline__ void ray_shade(const EngineDev& D, const RayView& R, 
     mid.y = (p1.y + p2.y) / 2;
     mid.z = (p1.z + p2.z) / 2;
   }
+  return mid;
+}
+__device__ __forceinline__ void ray_shade(const EngineDev& D, const RayView& R, RayCache& c, f3 hp, f3 sg,
+                                       f3 dw, uchar4* __restrict__ rgba, uchar4* __restrict__ normal, int idx) {
+  const f3 mid = ray_search(D, R, c, hp, sg);
   const int16_t fx = round_s16(mid.x), fy = round_s16(mid.y), fz = round_s16(mid.z);
   uint32_t col = 0;
   float prob = 0.0f;  // VoxelRGBW() / VoxelSEGM() defaults
@@ -136,6 +142,57 @@ __device__ __forceinline__ void ray_shade(const EngineDev& D, const RayView& R, 
   if (normal) normal[idx] = make_uchar4(f2u8(alpha * 255 + sh), f2u8(sh), f2u8(sh), 255);
 }
 
+// The hit as geometry (tsdf_raycast_surface, DESIGN.md "Pose tracking"): the zero crossing between the
+// march's last two samples prev > 0 >= cur, linear in the ray parameter, and from the voxel ray_shade
+// shades (the binary search's) the unit central-difference normal, the stored probability and
+// r, g, b, weight. A zero or non-finite gradient is no surface: zeros in every map.
+__device__ __forceinline__ void surface_store(const SurfaceOut& S, int idx, f3 p, f3 n, float depth, float prob,
+                                              uint32_t col) {
+  S.point[3 * idx] = p.x;
+  S.point[3 * idx + 1] = p.y;
+  S.point[3 * idx + 2] = p.z;
+  S.normal[3 * idx] = n.x;
+  S.normal[3 * idx + 1] = n.y;
+  S.normal[3 * idx + 2] = n.z;
+  if (S.depth) S.depth[idx] = depth;
+  if (S.prob) S.prob[idx] = prob;
+  if (S.rgbw) S.rgbw[idx] = col;
+}
+__device__ __forceinline__ void ray_surface(const EngineDev& D, const RayView& R, RayCache& c, f3 hp, f3 sg,
+                                            float prev, float cur, const FrameParams& P, const SurfaceOut& S,
+                                            int idx) {
+  const f3 p1 = {hp.x - sg.x, hp.y - sg.y, hp.z - sg.z};
+  const float s = prev / (prev - cur);
+  const f3 pv = {p1.x + s * sg.x, p1.y + s * sg.y, p1.z + s * sg.z};
+  const f3 pw = {pv.x * P.voxel, pv.y * P.voxel, pv.z * P.voxel};
+  const float depth = se3_apply(P.cq, P.ct, pw).z;
+  const f3 mid = ray_search(D, R, c, hp, sg);
+  const int16_t fx = round_s16(mid.x), fy = round_s16(mid.y), fz = round_s16(mid.z);
+  uint32_t col = 0;
+  float prob = 0.0f;  // VoxelRGBW() / VoxelSEGM() defaults
+  ray_block(D, R, c, fx >> kBlockLenBits, fy >> kBlockLenBits, fz >> kBlockLenBits);
+  if (c.idx >= 0) {
+    const uint8_t* blk = D.pool + (size_t)c.idx * kBlockBytes;
+    const int o = voxel_off(fx, fy, fz);
+    col = reinterpret_cast<const uint32_t*>(blk + kRgbwOffset)[o];
+    prob = reinterpret_cast<const float*>(blk + kProbOffset)[o];
+  }
+  const float gxp = ray_tsdf(D, R, c, (int16_t)(fx + 1), fy, fz);
+  const float gxn = ray_tsdf(D, R, c, (int16_t)(fx - 1), fy, fz);
+  const float gyp = ray_tsdf(D, R, c, fx, (int16_t)(fy + 1), fz);
+  const float gyn = ray_tsdf(D, R, c, fx, (int16_t)(fy - 1), fz);
+  const float gzp = ray_tsdf(D, R, c, fx, fy, (int16_t)(fz + 1));
+  const float gzn = ray_tsdf(D, R, c, fx, fy, (int16_t)(fz - 1));
+  const f3 nr = {gxp - gxn, gyp - gyn, gzp - gzn};
+  const float nn = dot3(nr, nr);
+  if (!(nn > 0.0f && nn < __builtin_inff())) {  // (NaN fails both)
+    surface_store(S, idx, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0u);
+    return;
+  }
+  const float len = sqrtf(nn);
+  surface_store(S, idx, pw, f3{nr.x / len, nr.y / len, nr.z / len}, depth, prob, col);
+}
+
 // The march (DESIGN.md 4 "Raycast") is VALU-issue bound: ~4.7 waves per SIMD each step ~135 times,
 // and a step in empty space (most of them) is only the position update and the region test. Along a
 // ray each coordinate of the reference's sequential float sums pos_{i+1} = fl(pos_i + step) is
@@ -144,10 +201,14 @@ __device__ __forceinline__ void ray_shade(const EngineDev& D, const RayView& R, 
 // (s = the step's sign), as one fma each (s_a * pos_a is exact, the sign of the rounded sum is the
 // sign of the exact one). The step counter is wave-uniform (scalar).
 // wg: this workgroup among the nwg of the raycast (16x16 tiles, gx per row); a launch of its own
-// passes its block index, the fused render + ingest launch (k_render_ingest) its raycast part's
+// passes its block index, the fused render + ingest launch (k_render_ingest) its raycast part's.
+// kSurf (k_raycast_surface): the same march, the hits written as float maps S (ray_surface) instead of
+// the shaded images; it keeps the march's two samples of the hit step.
+template <bool kSurf = false>
 __device__ __forceinline__ void raycast(const EngineDev& D, const FrameParams& P, float step_size,
                                         const ViewGrid& V, uint32_t* sbits, uchar4* __restrict__ rgba,
-                                        uchar4* __restrict__ normal, int wg, int gx, int nwg) {
+                                        uchar4* __restrict__ normal, int wg, int gx, int nwg,
+                                        const SurfaceOut& S = SurfaceOut{}) {
   // stage the bitmaps (all threads, before any ray returns)
   const int nw = V.n ? V.nw : 0;
   for (int i = threadIdx.x; i < nw; i += 256) sbits[i] = V.bits[i];
@@ -197,6 +258,7 @@ __device__ __forceinline__ void raycast(const EngineDev& D, const FrameParams& P
   bool active = valid && 1 < max_step;
   bool hit = false;
   f3 hit_pos = pos;
+  [[maybe_unused]] float hit_prev = 1.0f, hit_cur = 0.0f;
   float prev = 1.0f;
   if (active) prev = ray_tsdf(D, R, c, round_s16(pos.x), round_s16(pos.y), round_s16(pos.z));
   pos = {pos.x + sg.x, pos.y + sg.y, pos.z + sg.z};
@@ -257,6 +319,10 @@ __device__ __forceinline__ void raycast(const EngineDev& D, const FrameParams& P
         cur = reinterpret_cast<const float*>(D.pool + (size_t)ridx * kBlockBytes)[voxel_off(px, py, pz)];
         if (prev > 0 && cur <= 0 && (double)(prev - cur) <= 1.5) {
           hit_pos = pos;  // shaded after the march (below)
+          if constexpr (kSurf) {
+            hit_prev = prev;
+            hit_cur = cur;
+          }
           live = 0;  // frozen: an endless empty region from here on
           ne = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
           ridx = -1;
@@ -271,7 +337,12 @@ __device__ __forceinline__ void raycast(const EngineDev& D, const FrameParams& P
   // steps, and each step with a hit ran the whole shading (binary search + 7 lookups) for a few lanes.
   // The shading reads only the static volume (the block cache is a memo), so where it runs changes
   // nothing.
-  if (hit) {
+  if constexpr (kSurf) {
+    if (hit)
+      ray_surface(D, R, c, hit_pos, sg, hit_prev, hit_cur, P, S, idx);
+    else if (valid)
+      surface_store(S, idx, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0u);
+  } else if (hit) {
 #if defined(TSDF_EXP) && (TSDF_EXP & 8)  // experiment build: no shading (timing of the march alone)
     if (rgba) rgba[idx] = make_uchar4(255, 255, 255, 255);
 #else

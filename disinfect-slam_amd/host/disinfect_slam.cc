@@ -1,6 +1,9 @@
 // disinfect_slam.cc -- DISINFSystem's TSDF half (disinfect_slam/disinfect_slam.cc:3-116).
 #include "disinfect_slam.h"
 
+#include <limits>
+#include <stdexcept>
+
 namespace disinfect {
 
 static std::shared_ptr<TSDFSystem> make_tsdf(float voxel_size, float truncation, float max_depth,
@@ -25,6 +28,20 @@ void DISINFSystem::feed_rgbd_frame(const Mat& img_rgb, const Mat& img_depth, int
                                    const Mat& mask) {
   const SE3<float> posecam_P_world = camera_pose_manager_->query_pose(timestamp);
   TSDF_->IntegrateRaw(posecam_P_world, img_rgb, img_depth, mask, depthmap_factor_);
+}
+
+TrackResult DISINFSystem::track_rgbd_frame(const Mat& img_rgb, const Mat& img_depth, int64_t timestamp,
+                                           const Mat& mask) {
+  if (camera_pose_manager_->size() == 0)
+    throw std::logic_error("DISINFSystem::track_rgbd_frame: the first frame needs a registered pose");
+  Mat rgb_half, depth_half;
+  TSDF_->HalfRGBD(img_rgb, img_depth, mask, depthmap_factor_, &rgb_half, &depth_half);
+  // the newest registered pose: the nearest to a time after every timestamp
+  const SE3<float> guess = camera_pose_manager_->query_pose(std::numeric_limits<int64_t>::max());
+  const TrackResult r = TSDF_->Track(depth_half, guess);
+  camera_pose_manager_->register_valid_pose(timestamp, r.pose);
+  TSDF_->Integrate(r.pose, rgb_half, depth_half);
+  return r;
 }
 
 void DISINFSystem::register_camera_pose(int64_t timestamp, const SE3<float>& cam_T_world) {

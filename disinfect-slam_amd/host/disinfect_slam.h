@@ -3,7 +3,8 @@
 // feed_rgbd_frame and query_tsdf, over TSDFSystem on the MI355X engine. The ORB-SLAM3 tracker,
 // the segmentation network and the renderer are outside this engine: a tracker
 // registers its poses with register_camera_pose (what feed_stereo / feed_stereo_IMU do after
-// TrackStereo, disinfect_slam.cc:69-100).
+// TrackStereo, disinfect_slam.cc:69-100). Without a tracker, track_rgbd_frame takes the pose of each
+// frame from the volume itself (frame-to-model ICP, tsdf_track).
 #pragma once
 
 #include <memory>
@@ -24,6 +25,12 @@ class DISINFSystem {
   // disinfect_slam.cc:31-67: pose at `timestamp` [ms], x0.5 resize of rgb / depth / mask, depth
   // scale, mask -> depth 0, integrate (the resize / scale / mask run on the GPU)
   void feed_rgbd_frame(const Mat& img_rgb, const Mat& img_depth, int64_t timestamp, const Mat& mask = {});
+  // feed_rgbd_frame without an outside tracker: the frame's pose comes from the volume. The x0.5
+  // resize / depth scale / mask, then frame-to-model ICP of the half-size depth from the newest
+  // registered pose (TSDFSystem::Track), register_camera_pose(timestamp, result), integrate. The first
+  // frame needs a registered pose (throws std::logic_error without one): it fixes the world frame.
+  // A degenerate result registers and integrates at the last good estimate.
+  TrackResult track_rgbd_frame(const Mat& img_rgb, const Mat& img_depth, int64_t timestamp, const Mat& mask = {});
   void register_camera_pose(int64_t timestamp, const SE3<float>& cam_T_world);
   SE3<float> query_camera_pose(int64_t timestamp);                              // :108-111
   std::vector<VoxelSpatialTSDF> query_tsdf(const BoundingCube<float>& volumn);  // :113-116

@@ -85,6 +85,22 @@ void TSDFSystem::Render(const CameraParams& virtual_cam, const SE3<float> cam_T_
   tsdf_.RayCast(max_depth_, virtual_cam, cam_T_world, nullptr, img_normal);
 }
 
+TrackResult TSDFSystem::Track(const Mat& img_depth, const SE3<float>& guess_posecam_T_world,
+                              const tsdf_track_config* cfg) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  TrackResult r = tsdf_.Track(img_depth, max_depth_, intrinsics_, cam_T_posecam_ * guess_posecam_T_world, cfg);
+  r.pose = cam_T_posecam_.Inverse() * r.pose;
+  return r;
+}
+
+void TSDFSystem::HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor,
+                          Mat* rgb_out, Mat* depth_out) {
+  std::lock_guard<std::mutex> lock(mtx_read_);
+  tsdf_.HalfRGBD(img_rgb, img_depth_raw, mask, depth_factor, rgb_out, depth_out);
+}
+
 void TSDFSystem::Flush() {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });

@@ -58,6 +58,15 @@ class TSDFSystem {
   TriMesh QueryMesh(const BoundingCube<float>& volumn);  // TSDFGrid::ExtractMesh, under Query's lock
   void Render(const CameraParams& virtual_cam, const SE3<float> cam_T_world, Mat* img_normal);
 
+  // The pose of a depth frame (CV_32FC1 [m], the size the volume integrates) by frame-to-model ICP
+  // (TSDFGrid::Track): waits until every queued frame is integrated, then tracks under Query's lock.
+  // guess and the result are posecam_T_world, as Integrate takes it.
+  TrackResult Track(const Mat& img_depth, const SE3<float>& guess_posecam_T_world,
+                    const tsdf_track_config* cfg = nullptr);
+  // DISINFSystem::feed_rgbd_frame's preprocessing of a raw sensor frame alone (TSDFGrid::HalfRGBD)
+  void HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor, Mat* rgb_out,
+                Mat* depth_out);
+
   // block until every queued frame has been integrated (not in the reference; used by tests)
   void Flush();
   tsdf_stats Stats();

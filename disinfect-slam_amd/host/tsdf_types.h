@@ -214,4 +214,25 @@ struct TriMesh {
   std::vector<float> prob;     // 1 per vertex: high-touch probability
 };
 
+
+// The surface a raycast sees as float maps (tsdf_raycast_surface), rows x cols each: what a
+// frame-to-model tracker registers a depth frame against. A pixel without a surface holds zeros.
+struct SurfaceMaps {
+  int rows = 0, cols = 0;
+  std::vector<float> point;   // 3 per pixel: world position [m]
+  std::vector<float> normal;  // 3 per pixel: unit normal, world frame
+  std::vector<float> depth;   // camera z of point [m]; 0 = no surface
+  std::vector<float> prob;    // high-touch probability of the hit voxel
+  std::vector<uint8_t> rgbw;  // 4 per pixel: the hit voxel's r, g, b, fusion weight
+};
+
+// The pose of a depth frame against the volume (tsdf_track). degenerate: too few correspondences
+// or singular normal equations; pose is then the last good estimate (the guess when none was made).
+struct TrackResult {
+  SE3<float> pose;
+  bool degenerate = false;
+  int iterations = 0, inliers = 0;
+  float rmse = 0.0f;
+};
+
 }  // namespace disinfect

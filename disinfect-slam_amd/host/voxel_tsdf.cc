@@ -156,6 +156,61 @@ TriMesh TSDFGrid::ExtractMesh(const BoundingCube<float>* v, float missing_tsdf, 
   return m;
 }
 
+SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {
+  if (group_) throw std::runtime_error("TSDFGrid::RayCastSurface: not available on a sharded volume");
+  SurfaceMaps m;
+  m.rows = cam.img_h;
+  m.cols = cam.img_w;
+  const size_t n = (size_t)cam.img_h * cam.img_w;
+  m.point.resize(n * 3);
+  m.normal.resize(n * 3);
+  m.depth.resize(n);
+  m.prob.resize(n);
+  m.rgbw.resize(n * 4);
+  const tsdf_surface_out out{m.point.data(), m.normal.data(), m.depth.data(), m.prob.data(), m.rgbw.data(),
+                             TSDF_MEM_HOST};
+  const tsdf_intrinsics K{cam.intrinsics.fx, cam.intrinsics.fy, cam.intrinsics.cx, cam.intrinsics.cy};
+  const tsdf_pose P = to_pose(cam_T_world);
+  check_tsdf(tsdf_raycast_surface(engine_, &K, cam.img_w, cam.img_h, &P, max_depth, &out), "tsdf_raycast_surface");
+  return m;
+}
+
+TrackResult TSDFGrid::Track(const Mat& img_depth, float max_depth, const CameraIntrinsics<float>& intrinsics,
+                            const SE3<float>& guess, const tsdf_track_config* cfg) {
+  if (group_) throw std::runtime_error("TSDFGrid::Track: not available on a sharded volume");
+  if (img_depth.empty() || img_depth.type() != CV_32FC1)
+    throw std::invalid_argument("TSDFGrid::Track: expects a CV_32FC1 depth image");
+  const tsdf_intrinsics K{intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy};
+  const tsdf_pose G = to_pose(guess);
+  tsdf_track_result r;
+  check_tsdf(tsdf_track(engine_, img_depth.ptr<float>(), img_depth.cols, img_depth.rows, TSDF_MEM_HOST, &K, &G,
+                        max_depth, cfg, &r),
+             "tsdf_track");
+  const tsdf_pose& p = r.cam_T_world;
+  TrackResult out;
+  out.pose = SE3<float>(p.qx, p.qy, p.qz, p.qw, p.tx, p.ty, p.tz);
+  out.degenerate = r.status != TSDF_TRACK_OK;
+  out.iterations = r.iterations;
+  out.inliers = r.inliers;
+  out.rmse = r.rmse;
+  return out;
+}
+
+void TSDFGrid::HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor,
+                        Mat* rgb_out, Mat* depth_out) {
+  if (img_rgb.type() != CV_8UC3 || img_depth_raw.type() != CV_16UC1 || img_rgb.cols != img_depth_raw.cols ||
+      img_rgb.rows != img_depth_raw.rows || !rgb_out || !depth_out ||
+      (!mask.empty() && (mask.type() != CV_8UC1 || mask.total() != img_depth_raw.total())))
+    throw std::invalid_argument("TSDFGrid::HalfRGBD: expects CV_8UC3 rgb, CV_16UC1 depth, CV_8UC1 mask");
+  if (group_) throw std::runtime_error("TSDFGrid::HalfRGBD: not available on a sharded volume");
+  *rgb_out = Mat(img_rgb.rows / 2, img_rgb.cols / 2, CV_8UC3);
+  *depth_out = Mat(img_rgb.rows / 2, img_rgb.cols / 2, CV_32FC1);
+  check_tsdf(tsdf_rgbd_half(engine_, img_rgb.ptr<uint8_t>(), img_depth_raw.ptr<uint16_t>(),
+                            mask.empty() ? nullptr : mask.ptr<uint8_t>(), img_depth_raw.cols, img_depth_raw.rows,
+                            depth_factor, rgb_out->ptr<uint8_t>(), depth_out->ptr<float>(), TSDF_MEM_HOST),
+             "tsdf_rgbd_half");
+}
+
 tsdf_stats TSDFGrid::Stats(bool clear_status) {
   tsdf_stats s;
   if (group_)

@@ -49,6 +49,17 @@ class TSDFGrid {
   TriMesh ExtractMesh(const BoundingCube<float>* volumn = nullptr, float missing_tsdf = 0.99f,
                       int min_weight = 0);
 
+  // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
+  // throws std::runtime_error, like Track and HalfRGBD.
+  SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);
+  // the camera pose of a depth frame (CV_32FC1 [m]) by frame-to-model ICP from `guess` (tsdf_track;
+  // cfg null = KinectFusion's schedule)
+  TrackResult Track(const Mat& img_depth, float max_depth, const CameraIntrinsics<float>& intrinsics,
+                    const SE3<float>& guess_cam_T_world, const tsdf_track_config* cfg = nullptr);
+  // FeedRGBD's preprocessing alone (tsdf_rgbd_half): the half-size CV_8UC3 rgb and CV_32FC1 depth
+  void HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor, Mat* rgb_out,
+                Mat* depth_out);
+
   tsdf_stats Stats(bool clear_status = false);
   tsdf_engine* engine() { return engine_; }  // (NULL for a sharded volume)
   tsdf_group* group() { return group_; }      // (NULL for one engine)

@@ -837,6 +837,94 @@ class Engine:
             _lib.check(call(struct(a, n, m, TSDF_MEM_HOST)), "tsdf_extract_mesh_indexed")
         return a
 
+    # ---- pose tracking ----
+    @staticmethod
+    def _Kc(K):
+        return K._c() if isinstance(K, CameraIntrinsics) else _lib.Intrinsics(*[float(v) for v in K])
+
+    def raycast_surface(self, K, width, height, cam_T_world: SE3, max_depth: float, device: bool = False,
+                        maps=("point", "normal", "depth", "prob", "rgbw")) -> dict:
+        """What raycast() sees as float maps (tsdf_raycast_surface): point and normal (h, w, 3) f32 in
+        the world frame, depth (h, w) f32 (0 = no surface), prob (h, w) f32 and rgbw (h, w, 4) u8 of
+        the hit voxel; a pixel without a surface holds zeros. numpy arrays, or with device=True torch
+        tensors on this engine's GPU. `maps` selects the optional ones (point and normal always)."""
+        shapes = dict(point=(height, width, 3), normal=(height, width, 3), depth=(height, width),
+                      prob=(height, width), rgbw=(height, width, 4))
+        names = [k for k in shapes if k in ("point", "normal") or k in maps]
+        if device:
+            import torch
+            a = {k: torch.empty(shapes[k], dtype=torch.uint8 if k == "rgbw" else torch.float32,
+                                device=f"cuda:{self.device}") for k in names}
+        else:
+            a = {k: np.zeros(shapes[k], np.uint8 if k == "rgbw" else np.float32) for k in names}
+        out = _lib.SurfaceOut(*(_ptr(a.get(k)) for k in shapes), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        self._wait_torch(*a.values())
+        _lib.check(_lib.load().tsdf_raycast_surface(self._h, C.byref(self._Kc(K)), width, height,
+                                                    C.byref(cam_T_world._c()), max_depth, C.byref(out)),
+                   "tsdf_raycast_surface")
+        self._signal_torch(*a.values())
+        return a
+
+    def icp_linearize(self, depth, K, cam_T_world: SE3, model: dict, model_K, model_cam_T_world: SE3,
+                      stride: int, max_dist: float, max_depth: float):
+        """One point-to-plane linearisation (tsdf_icp_linearize) of the depth frame (h, w) f32 at the
+        estimate cam_T_world against the point / normal maps of raycast_surface(model_K, ...,
+        model_cam_T_world): (A (6, 6), b (6,), sum r^2, count) in float64. depth and the maps are all
+        numpy arrays or all torch tensors on this engine's GPU."""
+        dev = _is_torch_cuda(depth)
+        pt, nr = model["point"], model["normal"]
+        if dev != _is_torch_cuda(pt) or dev != _is_torch_cuda(nr):
+            raise ValueError("depth and the model maps must be all host or all device")
+        if dev:
+            d, pt, nr = depth.contiguous(), pt.contiguous(), nr.contiguous()
+        else:
+            d, pt, nr = _np(depth, np.float32), _np(pt, np.float32), _np(nr, np.float32)
+        h, w = d.shape
+        mh, mw = pt.shape[:2]
+        m = _lib.IcpModel(_ptr(pt), _ptr(nr), mw, mh, self._Kc(model_K), model_cam_T_world._c())
+        out = np.zeros(29, np.float64)
+        self._wait_torch(d, pt, nr)
+        _lib.check(_lib.load().tsdf_icp_linearize(self._h, _ptr(d), w, h, C.byref(self._Kc(K)),
+                                                  C.byref(cam_T_world._c()), C.byref(m), stride, max_dist,
+                                                  max_depth, _ptr(out), TSDF_MEM_DEVICE if dev else TSDF_MEM_HOST),
+                   "tsdf_icp_linearize")
+        self._signal_torch(d, pt, nr)
+        A = np.zeros((6, 6), np.float64)
+        A[np.triu_indices(6)] = out[:21]
+        A = A + np.triu(A, 1).T
+        return A, out[21:27].copy(), float(out[27]), int(out[28])
+
+    def track(self, depth, K, guess: SE3, max_depth: float, **cfg):
+        """The pose of a depth frame (h, w) f32 against the volume (tsdf_track): frame-to-model
+        point-to-plane ICP from `guess`. Keywords are tsdf_track_config's fields (levels, stride,
+        iterations, max_dist, eps_rot, eps_trans, min_inliers). Returns (SE3 cam_T_world, info) with
+        info = dict(status, iterations, inliers, rmse); status 1 (degenerate) keeps the last good estimate."""
+        L = _lib.load()
+        c = _lib.TrackConfig()
+        L.tsdf_track_config_default(C.byref(c))
+        for k, v in cfg.items():
+            if k in ("stride", "iterations"):
+                v = list(v) + [1] * (3 - len(v))
+                setattr(c, k, (C.c_int * 3)(*[int(x) for x in v]))
+            elif k in ("levels", "min_inliers"):
+                setattr(c, k, int(v))
+            elif k in ("max_dist", "eps_rot", "eps_trans"):
+                setattr(c, k, float(v))
+            else:
+                raise TypeError(f"track: unknown option {k}")
+        dev = _is_torch_cuda(depth)
+        d = depth.contiguous() if dev else _np(depth, np.float32)
+        h, w = d.shape
+        r = _lib.TrackResult()
+        self._wait_torch(d)
+        _lib.check(L.tsdf_track(self._h, _ptr(d), w, h, TSDF_MEM_DEVICE if dev else TSDF_MEM_HOST,
+                                C.byref(self._Kc(K)), C.byref(guess._c()), max_depth, C.byref(c), C.byref(r)),
+                   "tsdf_track")
+        self._signal_torch(d)
+        p = r.cam_T_world
+        return (SE3((p.qx, p.qy, p.qz, p.qw), (p.tx, p.ty, p.tz)),
+                dict(status=int(r.status), iterations=int(r.iterations), inliers=int(r.inliers), rmse=float(r.rmse)))
+
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()
         b = None if bounds is None else np.ascontiguousarray(

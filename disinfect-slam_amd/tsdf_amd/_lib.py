@@ -110,6 +110,53 @@ class MeshOut(C.Structure):
     ]
 
 
+class SurfaceOut(C.Structure):
+    _fields_ = [
+        ("point", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("prob", C.c_void_p),
+        ("rgbw", C.c_void_p),
+        ("mem_kind", C.c_int),
+    ]
+
+
+class IcpModel(C.Structure):
+    _fields_ = [
+        ("point", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("K", Intrinsics),
+        ("cam_T_world", Pose),
+    ]
+
+
+class TrackConfig(C.Structure):
+    _fields_ = [
+        ("levels", C.c_int),
+        ("stride", C.c_int * 3),
+        ("iterations", C.c_int * 3),
+        ("max_dist", C.c_float),
+        ("eps_rot", C.c_float),
+        ("eps_trans", C.c_float),
+        ("min_inliers", C.c_int),
+    ]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [
+        ("cam_T_world", Pose),
+        ("status", C.c_int32),
+        ("iterations", C.c_int32),
+        ("inliers", C.c_int32),
+        ("rmse", C.c_float),
+    ]
+
+
+TSDF_TRACK_OK = 0
+TSDF_TRACK_DEGENERATE = 1
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -130,6 +177,7 @@ EXPORTS = [
     "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats", "tsdf_group_query", "tsdf_group_raycast",
     "tsdf_group_stream_signal",
     "tsdf_extract_mesh_indexed",
+    "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track_config_default", "tsdf_track",
 ]
 
 _lib = None
@@ -205,6 +253,13 @@ def load(path: str | None = None):
     L.tsdf_query.argtypes = [P, P, P, i64, C.POINTER(i64)]
     L.tsdf_extract_mesh.argtypes = [P, P, f, i, P, i64, C.POINTER(i64), i]
     L.tsdf_extract_mesh_indexed.argtypes = [P, P, f, i, C.POINTER(MeshOut), C.POINTER(i64), C.POINTER(i64)]
+    L.tsdf_raycast_surface.argtypes = [P, C.POINTER(Intrinsics), i, i, C.POINTER(Pose), f, C.POINTER(SurfaceOut)]
+    L.tsdf_icp_linearize.argtypes = [P, P, i, i, C.POINTER(Intrinsics), C.POINTER(Pose), C.POINTER(IcpModel), i, f, f,
+                                     P, i]
+    L.tsdf_track_config_default.argtypes = [C.POINTER(TrackConfig)]
+    L.tsdf_track_config_default.restype = None
+    L.tsdf_track.argtypes = [P, P, i, i, i, C.POINTER(Intrinsics), C.POINTER(Pose), f, C.POINTER(TrackConfig),
+                             C.POINTER(TrackResult)]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -251,7 +306,7 @@ def load(path: str | None = None):
                  "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_integrate",
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
-                 "tsdf_extract_mesh_indexed"):
+                 "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -441,6 +441,88 @@ typedef struct tsdf_mesh_out {
 int tsdf_extract_mesh_indexed(tsdf_engine* e, const float* bounds, float missing_tsdf, int min_weight,
                               const tsdf_mesh_out* out, int64_t* num_vertices, int64_t* num_triangles);
 
+/* ---- Pose tracking against the volume (frame-to-model point-to-plane ICP, KinectFusion style) ----
+ * All three calls complete a pending pipelined frame first and are not available on a shard engine
+ * (shard_count > 1): TSDF_ERR_INVALID_ARG.
+ *
+ * tsdf_raycast_surface: what tsdf_raycast sees, as float maps. The march is tsdf_raycast's (view grid,
+ * step = truncation / 2, sequential position sums, hit test prev > 0 && cur <= 0 && prev - cur <= 1.5):
+ * a pixel has a surface only where tsdf_raycast writes alpha 255, at the same step. With hp the
+ * position at the hit step and sg the step's increment (voxel units), prev / cur the march's own two
+ * samples (prev = +1 after a missing block or an empty region):
+ *   p1 = hp - sg; s = prev / (prev - cur); pv = p1 + s * sg; point = pv * voxel_size;
+ *   depth = (cam_T_world * point).z
+ * normal, prob and rgbw come from the voxel the shaded images use (the end of their binary search):
+ * nr = the six-neighbour central difference (a missing neighbour reads +1), normal = nr / sqrt(nr . nr),
+ * prob and rgbw that voxel's stored values (0 when its block is missing). nr . nr zero or not finite:
+ * no surface. A pixel without a surface holds zeros in every map. fp32, one operation at a time. */
+typedef struct tsdf_surface_out {
+  float* point;    /* H x W x 3: world position of the surface [m] */
+  float* normal;   /* H x W x 3: unit normal, world frame, toward increasing tsdf */
+  float* depth;    /* H x W: camera z of point [m]; 0 = no surface       NULL = skip */
+  float* prob;     /* H x W: high-touch probability of the hit voxel      NULL = skip */
+  uint8_t* rgbw;   /* H x W x 4: the hit voxel's stored r, g, b, weight (4-byte aligned)  NULL = skip */
+  int mem_kind;    /* TSDF_MEM_HOST or TSDF_MEM_DEVICE, all pointers alike */
+} tsdf_surface_out;
+int tsdf_raycast_surface(tsdf_engine* e, const tsdf_intrinsics* K, int width, int height,
+                         const tsdf_pose* cam_T_world, float max_depth, const tsdf_surface_out* out);
+
+/* tsdf_icp_linearize: one Gauss-Newton linearisation of the point-to-plane error of a depth frame at
+ * the estimate cam_T_world against the maps of a tsdf_raycast_surface call. For every pixel (u, v)
+ * with u % stride == 0 && v % stride == 0, in fp32 op by op:
+ *   d = depth[v * W + u], kept if d > 0 && d <= max_depth; pc = (ray.x * d, ray.y * d, d) with
+ *   ray = K^-1 (u, v, 1); pw = world_T_cam * pc; pm = model.cam_T_world * pw, kept if pm.z > 0;
+ *   um = rint(fx_m * (pm.x / pm.z) + cx_m), vm likewise (half to even), kept inside the model map;
+ *   q = point[vm, um], n = normal[vm, um], kept if n != 0; e = pw - q, kept if e . e <= max_dist^2;
+ *   r = n . e; J = (pw x n, n)
+ * and the sums below over the kept pixels in double (every product exact). The same arguments give
+ * the same 29 doubles bit for bit: no atomics, a fixed addition tree. */
+typedef struct tsdf_icp_model {          /* the maps of a tsdf_raycast_surface call */
+  const float* point; const float* normal;
+  int width, height; tsdf_intrinsics K; tsdf_pose cam_T_world;
+} tsdf_icp_model;
+/* out[0..20]  = upper triangle of A = sum J J^T, row-major (i <= j)
+   out[21..26] = b = sum J r
+   out[27]     = sum r^2
+   out[28]     = count */
+int tsdf_icp_linearize(tsdf_engine* e, const float* depth, int width, int height,
+                       const tsdf_intrinsics* K, const tsdf_pose* cam_T_world /* estimate */,
+                       const tsdf_icp_model* model, int stride, float max_dist, float max_depth,
+                       double* out29 /* host */, int mem_kind /* depth and the model maps */);
+
+/* tsdf_track: the pose of a depth frame. One tsdf_raycast_surface of the model from the guess with
+ * (K, width, height, max_depth). The loop's model normals are taken from that call's points, not its
+ * normal map (nearest-voxel central differences are too coarse where a depth pixel spans several
+ * voxels): at a pixel whose four neighbours and itself have a surface,
+ * c = (p[v+1][u] - p[v-1][u]) x (p[v][u+1] - p[v][u-1]), turned to face the camera, over its length;
+ * no normal (the pixel is not a correspondence) on the border, beside a hole, or where c is more than
+ * acos(0.3) off the viewing ray. Then per level up to iterations[l] times: tsdf_icp_linearize at
+ * stride[l]; on the host in double the Cholesky solve of A xi = -b, xi = (omega, t); world_T_cam <-
+ * (exp([omega]x), t) * world_T_cam; the estimate rounded to a float unit quaternion and translation.
+ * TSDF_TRACK_DEGENERATE (count < min_inliers, or a Cholesky pivot <= 0 or not finite; an all-zero
+ * depth frame is the first) stops with the last good estimate; the call still returns TSDF_OK.
+ * rmse = sqrt(sum r^2 / count) and inliers = count of the last linearisation. */
+typedef struct tsdf_track_config {
+  int levels;             /* 1..3 */
+  int stride[3];          /* coarse to fine */
+  int iterations[3];
+  float max_dist;         /* [m] correspondence gate */
+  float eps_rot;          /* stop a level early when |omega| <= eps_rot and */
+  float eps_trans;        /*   |t| <= eps_trans; 0 = never */
+  int min_inliers;        /* fewer -> TSDF_TRACK_DEGENERATE */
+} tsdf_track_config;
+/* Defaults: levels = 3, stride {4, 2, 1}, iterations {4, 5, 10} (KinectFusion's schedule), max_dist =
+ * 0.1 (its 10 cm gate), eps_rot = eps_trans = 0, min_inliers = 6 (the algebraic minimum) */
+void tsdf_track_config_default(tsdf_track_config* cfg);
+#define TSDF_TRACK_OK 0
+#define TSDF_TRACK_DEGENERATE 1
+typedef struct tsdf_track_result {
+  tsdf_pose cam_T_world; int32_t status, iterations, inliers; float rmse;
+} tsdf_track_result;
+int tsdf_track(tsdf_engine* e, const float* depth, int width, int height, int mem_kind,
+               const tsdf_intrinsics* K, const tsdf_pose* guess_cam_T_world, float max_depth,
+               const tsdf_track_config* cfg /* NULL = defaults */, tsdf_track_result* out);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
