@@ -328,6 +328,29 @@ __global__ void k_icp_partial(IcpParams I, double* part);
 constexpr int kIcpChunks = 32;
 static_assert(kIcpChunks * kIcpSums <= 1024, "k_icp_final's workgroup");
 __global__ void k_icp_final(const double* part, int nwg, double* out);
+// UV dose (tsdf_dose.hip; DESIGN.md "UV dose"): receivers (points, normals, dose; n of them), the m
+// emitters as {x, y, z, energy} and the configuration in voxel units where the march needs it
+struct DoseParams {
+  const float* points;
+  const float* normals;
+  float* dose;
+  int64_t n;
+  const float4* emit;
+  int m;
+  float voxel, bias, sv;  // sv = step / voxel: the sample spacing in voxels
+  float min_range, max_range, offset;
+  int min_weight;
+  int ox, oy, oz;         // the block grid's origin (block coordinates) when V.n != 0
+};
+// the unit central-difference normal of the voxel nearest to each point (hash lookups); one lane per point
+__global__ void k_point_normals(EngineDev D, const float* points, int64_t n, float voxel, float offset,
+                                float* normals);
+// one lane per receiver, the emitters in order; V.n == 0: hash lookups only (dynamic LDS: V.nw words)
+__global__ void k_uv_dose(EngineDev D, DoseParams A, ViewGrid V);
+// what the block grid of a k_uv_dose call has to cover: box[0..2] / box[3..5] the least / greatest voxel
+// coordinate of the ray origins of receivers some emitter irradiates (integer min / max: any order gives
+// the same box), eflag[k] = 1 for an emitter in range of a receiver. box starts at {INT_MAX x 3, INT_MIN x 3}.
+__global__ void k_dose_bounds(DoseParams A, int32_t* box, int32_t* eflag);
 // frame n's raycast (R, V: its view grid, built before) + frame n + 1's ingest (k_ingest_dda<1024>) in
 // one launch: nray raycast workgroups (rgx tiles per row) first, then kVisWorkgroups + tiles (tsdf_alloc.hip)
 __global__ void k_render_ingest(EngineDev D, FrameParams R, float step_size, ViewGrid V, uchar4* rgba,

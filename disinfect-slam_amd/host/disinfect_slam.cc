@@ -58,4 +58,19 @@ std::vector<VoxelSpatialTSDF> DISINFSystem::query_tsdf(const BoundingCube<float>
 
 TriMesh DISINFSystem::query_mesh(const BoundingCube<float>& volumn) { return TSDF_->QueryMesh(volumn); }
 
+void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {
+  const size_t nv = mesh.verts.size() / 3;
+  if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);
+  if (mesh.dose.empty()) mesh.dose.assign(nv, 0.0f);
+  if (mesh.normals.size() != mesh.verts.size() || mesh.dose.size() != nv)
+    throw std::invalid_argument("DISINFSystem::irradiate: normals / dose do not match the vertices");
+  tsdf_uv_config c;
+  if (cfg)
+    c = *cfg;
+  else
+    tsdf_uv_config_default(TSDF_->engine(), &c);
+  c.sample_offset = 0.5f;
+  TSDF_->AccumulateDose(mesh.verts, mesh.normals, emitters, &mesh.dose, &c);
+}
+
 }  // namespace disinfect

@@ -11,6 +11,7 @@
 
 #include "pose_manager.h"
 #include "tsdf_module.h"
+#include "uv_dose.h"
 
 namespace disinfect {
 
@@ -37,6 +38,12 @@ class DISINFSystem {
   // the surface in `volumn` as an indexed mesh with colour and high-touch probability: what tsdfCb
   // builds from query_tsdf's voxels on the CPU (ros_offline.cc:286-313), extracted on the GPU
   TriMesh query_mesh(const BoundingCube<float>& volumn);
+  // The UV dose [J/m^2] the emitters (e.g. tube_emitters of a lamp pose and dwell time) add to every
+  // vertex of a query_mesh result, shadowed by the volume (sample_offset 0.5: the mesh's half-voxel
+  // shift; cfg null = the defaults). Fills mesh.normals when empty (the nearest voxel's unit normal) and
+  // accumulates into mesh.dose, sized and zeroed when empty. carry_dose (uv_dose.h) moves the dose of an
+  // earlier extraction over by mesh.keys.
+  void irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg = nullptr);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

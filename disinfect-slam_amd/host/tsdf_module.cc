@@ -2,6 +2,7 @@
 #include "tsdf_module.h"
 
 #include <cstdio>
+#include <stdexcept>
 
 namespace disinfect {
 
@@ -93,6 +94,30 @@ TrackResult TSDFSystem::Track(const Mat& img_depth, const SE3<float>& guess_pose
   TrackResult r = tsdf_.Track(img_depth, max_depth_, intrinsics_, cam_T_posecam_ * guess_posecam_T_world, cfg);
   r.pose = cam_T_posecam_.Inverse() * r.pose;
   return r;
+}
+
+std::vector<float> TSDFSystem::SurfaceNormals(const std::vector<float>& points, float sample_offset) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.SurfaceNormals(points, sample_offset);
+}
+
+void TSDFSystem::AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
+                                const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
+                                const tsdf_uv_config* cfg) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  tsdf_.AccumulateDose(points, normals, emitters, dose, cfg);
+}
+
+void TSDFSystem::ImportBlocks(const void* records, int64_t n, bool replace) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  if (!tsdf_.engine()) throw std::runtime_error("TSDFSystem::ImportBlocks: not available on a sharded volume");
+  check_tsdf(tsdf_import_blocks(tsdf_.engine(), records, n, TSDF_MEM_HOST, replace ? 1 : 0), "tsdf_import_blocks");
 }
 
 void TSDFSystem::HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor,

@@ -67,6 +67,18 @@ class TSDFSystem {
   void HalfRGBD(const Mat& img_rgb, const Mat& img_depth_raw, const Mat& mask, float depth_factor, Mat* rgb_out,
                 Mat* depth_out);
 
+  // UV dose (TSDFGrid::SurfaceNormals / AccumulateDose): like Track, they wait until every queued frame
+  // is integrated and run under Query's lock
+  std::vector<float> SurfaceNormals(const std::vector<float>& points, float sample_offset);
+  void AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
+                      const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
+                      const tsdf_uv_config* cfg = nullptr);
+  // the volume replaced by (replace) or extended with n block records (tsdf_import_blocks, host memory;
+  // one unsharded volume only), after every queued frame
+  void ImportBlocks(const void* records, int64_t n, bool replace);
+  // (NULL for a sharded volume; for tsdf_uv_config_default and the like, not for calls beside the worker)
+  tsdf_engine* engine() { return tsdf_.engine(); }
+
   // block until every queued frame has been integrated (not in the reference; used by tests)
   void Flush();
   tsdf_stats Stats();

@@ -212,6 +212,10 @@ struct TriMesh {
   std::vector<int32_t> tris;   // 3 vertex indices per triangle
   std::vector<uint8_t> rgba;   // 4 per vertex: r, g, b, fusion weight
   std::vector<float> prob;     // 1 per vertex: high-touch probability
+  std::vector<int32_t> keys;   // 4 per vertex: gx, gy, gz, axis -- the vertex's identity across extractions
+  // UV dose (DISINFSystem::irradiate); empty unless filled
+  std::vector<float> normals;  // 3 per vertex: unit normal of the nearest voxel (zeros: none)
+  std::vector<float> dose;     // 1 per vertex: accumulated UV dose [J/m^2]
 };
 
 

@@ -142,11 +142,13 @@ TriMesh TSDFGrid::ExtractMesh(const BoundingCube<float>* v, float missing_tsdf, 
   m.tris.resize((size_t)nt * 3);
   m.rgba.resize((size_t)nv * 4);
   m.prob.resize((size_t)nv);
+  m.keys.resize((size_t)nv * 4);
   if (nv == 0 && nt == 0) return m;
   tsdf_mesh_out out{};
   out.positions = m.verts.data();
   out.rgba = m.rgba.data();
   out.prob = m.prob.data();
+  out.keys = m.keys.data();
   out.indices = m.tris.data();
   out.vertex_capacity = nv;
   out.triangle_capacity = nt;
@@ -154,6 +156,27 @@ TriMesh TSDFGrid::ExtractMesh(const BoundingCube<float>* v, float missing_tsdf, 
   check_tsdf(tsdf_extract_mesh_indexed(engine_, v ? b : nullptr, missing_tsdf, min_weight, &out, &nv, &nt),
              "tsdf_extract_mesh_indexed");
   return m;
+}
+
+std::vector<float> TSDFGrid::SurfaceNormals(const std::vector<float>& points, float sample_offset) {
+  if (group_) throw std::runtime_error("TSDFGrid::SurfaceNormals: not available on a sharded volume");
+  if (points.size() % 3) throw std::invalid_argument("TSDFGrid::SurfaceNormals: 3 floats per point");
+  std::vector<float> normals(points.size());
+  check_tsdf(tsdf_surface_normals(engine_, points.data(), (int64_t)(points.size() / 3), sample_offset, normals.data(),
+                                  TSDF_MEM_HOST),
+             "tsdf_surface_normals");
+  return normals;
+}
+
+void TSDFGrid::AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
+                              const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
+                              const tsdf_uv_config* cfg) {
+  if (group_) throw std::runtime_error("TSDFGrid::AccumulateDose: not available on a sharded volume");
+  if (!dose || points.size() % 3 || normals.size() != points.size() || dose->size() * 3 != points.size())
+    throw std::invalid_argument("TSDFGrid::AccumulateDose: 3 floats per point and normal, 1 per dose");
+  check_tsdf(tsdf_uv_dose(engine_, points.data(), normals.data(), (int64_t)dose->size(), emitters.data(),
+                          (int32_t)emitters.size(), cfg, dose->data(), TSDF_MEM_HOST),
+             "tsdf_uv_dose");
 }
 
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {

@@ -49,6 +49,15 @@ class TSDFGrid {
   TriMesh ExtractMesh(const BoundingCube<float>* volumn = nullptr, float missing_tsdf = 0.99f,
                       int min_weight = 0);
 
+  // UV dose on surface points (tsdf_surface_normals / tsdf_uv_dose; 3 floats per point and normal):
+  // the nearest voxel's unit normal of each point, and the dose [J/m^2] the emitters add to each
+  // receiver, shadowed by the volume (cfg null = the defaults). sample_offset: 0.5 for ExtractMesh's
+  // vertices, 0 for RayCastSurface's points. Not available on a sharded volume: std::runtime_error.
+  std::vector<float> SurfaceNormals(const std::vector<float>& points, float sample_offset);
+  void AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
+                      const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
+                      const tsdf_uv_config* cfg = nullptr);
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

@@ -925,6 +925,79 @@ class Engine:
         return (SE3((p.qx, p.qy, p.qz, p.qw), (p.tx, p.ty, p.tz)),
                 dict(status=int(r.status), iterations=int(r.iterations), inliers=int(r.inliers), rmse=float(r.rmse)))
 
+    # ---- UV dose ----
+    def _points(self, a, device, cols=3):
+        """An (n, cols) f32 array as the call takes it: a contiguous numpy array, or with device=True a
+        contiguous torch tensor on this engine's GPU."""
+        if device:
+            import torch
+            t = a if _is_torch_cuda(a) else torch.as_tensor(np.asarray(a, np.float32), device=f"cuda:{self.device}")
+            t = t.to(torch.float32).contiguous()
+        else:
+            if _is_torch_cuda(a):
+                raise ValueError("device tensors need device=True")
+            t = np.ascontiguousarray(a, dtype=np.float32)
+        if (cols == 1 and t.ndim != 1) or (cols > 1 and (t.ndim != 2 or t.shape[1] != cols)):
+            raise ValueError(f"expected shape (n{', %d' % cols if cols > 1 else ''}), got {tuple(t.shape)}")
+        return t
+
+    def surface_normals(self, points, sample_offset: float = 0.0, device: bool = False):
+        """The unit normal of the voxel nearest to each of the (n, 3) world points (tsdf_surface_normals):
+        its six-neighbour central difference over its length, zeros where that is zero or not finite.
+        sample_offset 0.5 for mesh vertices (the mesh's half-voxel shift), 0 for raycast_surface points.
+        numpy in and out, or with device=True torch tensors on this engine's GPU."""
+        p = self._points(points, device)
+        if device:
+            import torch
+            out = torch.empty_like(p)
+        else:
+            out = np.zeros_like(p)
+        self._wait_torch(p, out)
+        _lib.check(_lib.load().tsdf_surface_normals(self._h, _ptr(p), p.shape[0], float(sample_offset), _ptr(out),
+                                                    TSDF_MEM_DEVICE if device else TSDF_MEM_HOST),
+                   "tsdf_surface_normals")
+        self._signal_torch(p, out)
+        return out
+
+    def uv_dose(self, points, normals, emitters, dose=None, device: bool = False, **cfg):
+        """The UV dose [J/m^2] the point emitters add to each receiver (tsdf_uv_dose): inverse-square and
+        cosine law, an emitter counting only where a shadow ray through the volume reaches it. points,
+        normals (n, 3) f32 (normals=None: surface_normals(points, sample_offset)); emitters (m, 4) f32
+        rows x, y, z, energy [J] on the host (uv.tube_emitters); dose (n,) f32 to accumulate into (None:
+        zeros; a given array or tensor of the right kind is updated in place). Keywords are
+        tsdf_uv_config's fields (bias, step, min_range, max_range, sample_offset, min_weight, use_grid).
+        Returns the dose array, or with device=True the tensor."""
+        L = _lib.load()
+        c = _lib.UvConfig()
+        L.tsdf_uv_config_default(self._h, C.byref(c))
+        for k, v in cfg.items():
+            if k in ("min_weight", "use_grid"):
+                setattr(c, k, int(v))
+            elif k in ("bias", "step", "min_range", "max_range", "sample_offset"):
+                setattr(c, k, float(v))
+            else:
+                raise TypeError(f"uv_dose: unknown option {k}")
+        p = self._points(points, device)
+        nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
+        em = np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
+        n = p.shape[0]
+        if dose is None:
+            if device:
+                import torch
+                d = torch.zeros((n,), dtype=torch.float32, device=p.device)
+            else:
+                d = np.zeros(n, np.float32)
+        else:
+            d = self._points(dose, device, cols=1)
+        if tuple(nr.shape) != tuple(p.shape) or d.shape[0] != n:
+            raise ValueError("points, normals and dose do not match")
+        self._wait_torch(p, nr, d)
+        rc = L.tsdf_uv_dose(self._h, _ptr(p), _ptr(nr), n, _ptr(em), em.shape[0], C.byref(c), _ptr(d),
+                            TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        self._signal_torch(p, nr, d)
+        _lib.check(rc, "tsdf_uv_dose")
+        return d
+
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()
         b = None if bounds is None else np.ascontiguousarray(

@@ -157,6 +157,23 @@ class TrackResult(C.Structure):
 TSDF_TRACK_OK = 0
 TSDF_TRACK_DEGENERATE = 1
 
+
+class UvEmitter(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("energy", C.c_float)]
+
+
+class UvConfig(C.Structure):
+    _fields_ = [
+        ("bias", C.c_float),
+        ("step", C.c_float),
+        ("min_range", C.c_float),
+        ("max_range", C.c_float),
+        ("sample_offset", C.c_float),
+        ("min_weight", C.c_int),
+        ("use_grid", C.c_int),
+    ]
+
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -178,6 +195,7 @@ EXPORTS = [
     "tsdf_group_stream_signal",
     "tsdf_extract_mesh_indexed",
     "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track_config_default", "tsdf_track",
+    "tsdf_uv_config_default", "tsdf_surface_normals", "tsdf_uv_dose",
 ]
 
 _lib = None
@@ -260,6 +278,10 @@ def load(path: str | None = None):
     L.tsdf_track_config_default.restype = None
     L.tsdf_track.argtypes = [P, P, i, i, i, C.POINTER(Intrinsics), C.POINTER(Pose), f, C.POINTER(TrackConfig),
                              C.POINTER(TrackResult)]
+    L.tsdf_uv_config_default.argtypes = [P, C.POINTER(UvConfig)]
+    L.tsdf_uv_config_default.restype = None
+    L.tsdf_surface_normals.argtypes = [P, P, i64, f, P, i]
+    L.tsdf_uv_dose.argtypes = [P, P, P, i64, P, C.c_int32, C.POINTER(UvConfig), P, i]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -306,7 +328,8 @@ def load(path: str | None = None):
                  "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_integrate",
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
-                 "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track"):
+                 "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
+                 "tsdf_surface_normals", "tsdf_uv_dose"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

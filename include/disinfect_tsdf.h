@@ -523,6 +523,57 @@ int tsdf_track(tsdf_engine* e, const float* depth, int width, int height, int me
                const tsdf_intrinsics* K, const tsdf_pose* guess_cam_T_world, float max_depth,
                const tsdf_track_config* cfg /* NULL = defaults */, tsdf_track_result* out);
 
+/* ---- UV dose on surface points (no reference counterpart: its planner receives the mesh over ROS and
+ * irradiates off-board) ----
+ * How much UV energy per area each surface point has received from a list of point emitters: the
+ * inverse-square and cosine law, with a shadow ray marched through the volume. Receivers are any surface
+ * points with unit normals: the vertices of tsdf_extract_mesh_indexed (sample_offset 0.5: the mesh's
+ * half-voxel shift) or the maps of tsdf_raycast_surface (sample_offset 0). Both calls complete a pending
+ * pipelined frame first, run asynchronously on the engine stream for device memory and copy for host
+ * memory, are not available on a shard engine (shard_count > 1: TSDF_ERR_INVALID_ARG), only read the
+ * volume and set no status bits. n == 0 (or m == 0) is TSDF_OK with nothing written.
+ * Everything below is fp32, one operation at a time; dot3(a, b) = a.x b.x + (a.y b.y + a.z b.z),
+ * round() is half away from zero, saturated to int16.
+ *
+ * tsdf_surface_normals: per component v = round(p / voxel_size - sample_offset); nr = the six-neighbour
+ * central difference of the tsdf at v (a voxel of a missing block reads +1, as tsdf_raycast_surface's);
+ * nn = dot3(nr, nr); the normal is nr / sqrtf(nn), or zeros unless nn > 0 && nn < inf.
+ *
+ * tsdf_uv_dose, receiver i with position p and normal n: an all-zero normal leaves dose[i] unchanged.
+ * Otherwise acc = 0 and for the emitters k = 0 .. m - 1 in order: d = e_k - p, r2 = dot3(d, d),
+ * r = sqrtf(r2), c = dot3(n, d) / r; the emitter counts when r >= min_range && r <= max_range && c > 0
+ * and it is visible, and then acc = acc + (energy_k * 0.07957747f) * (c / r2)   [1 / (4 pi)].
+ * Finally dose[i] = dose[i] + acc. The order of the sum is part of the contract (no atomics).
+ * Visibility: o = p + bias * n; ov = o / voxel_size - sample_offset; ev = e_k / voxel_size -
+ * sample_offset; dv = ev - ov; L = sqrtf(dot3(dv, dv)); sv = step / voxel_size. With !(L > 0) the only
+ * sample is s_0 = ov; otherwise sg = (dv / L) * sv per component, J = (int)(L / sv), and the samples are
+ * s_j = ov + (float)j * sg for j = 0 .. J (one product and one sum per component, no running sums).
+ * Sample j occludes when the voxel round(s_j) lies in an allocated block, its fusion weight is
+ * >= min_weight and its tsdf is <= 0. The emitter is visible when no sample occludes.
+ * Also required: step > 0, max_range >= min_range, |bias| <= max_range (they bound a ray's samples). */
+typedef struct tsdf_uv_emitter {
+  float x, y, z; /* world position [m] */
+  float energy;  /* radiant energy emitted there [J] = power [W] * dwell [s] */
+} tsdf_uv_emitter;
+typedef struct tsdf_uv_config {
+  float bias;          /* [m] shadow ray starts at p + bias * n */
+  float step;          /* [m] shadow-ray sample spacing */
+  float min_range;     /* [m] > 0; an emitter nearer than this contributes nothing */
+  float max_range;     /* [m] one farther contributes nothing; max_range / step <= 65536 */
+  float sample_offset; /* [voxels] voxel coordinate of world x is x / voxel_size - sample_offset:
+                          0 for tsdf_raycast_surface points, 0.5 for mesh vertices */
+  int min_weight;      /* a voxel occludes only with fusion weight >= this */
+  int use_grid;        /* 1: the call may build a dense block grid over the rays to skip empty space;
+                          0: hash lookups only. Same bytes either way */
+} tsdf_uv_config;
+/* bias = 2 voxels, step = 1 voxel, min_range 0.05, max_range 5, sample_offset 0, min_weight 1, use_grid 1 */
+void tsdf_uv_config_default(const tsdf_engine* e, tsdf_uv_config* cfg);
+int tsdf_surface_normals(tsdf_engine* e, const float* points, int64_t n, float sample_offset,
+                         float* normals, int mem_kind);
+int tsdf_uv_dose(tsdf_engine* e, const float* points, const float* normals, int64_t n,
+                 const tsdf_uv_emitter* emitters /* host */, int32_t m, const tsdf_uv_config* cfg /* NULL = defaults */,
+                 float* dose /* n, in/out [J/m^2] */, int mem_kind /* points, normals, dose alike */);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
