@@ -11,7 +11,9 @@ OUT=$ROOT/disinfect-slam_amd/build/var_$NAME
 mkdir -p "$OUT"
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function -I$TMP/include -I$TMP/disinfect-slam_amd/csrc $FLAGS"
 pids=()
-for f in tsdf_alloc tsdf_fuse tsdf_extract tsdf_mesh tsdf_frontend tsdf_engine; do
+for src in "$TMP"/disinfect-slam_amd/csrc/*.hip; do  # that revision's sources, but the test-only self-check
+  f=$(basename "$src" .hip)
+  [ "$f" = tsdf_selfcheck ] && continue
   /opt/rocm/bin/hipcc $HIPFLAGS -c "$TMP/disinfect-slam_amd/csrc/$f.hip" -o "$OUT/$f.o" & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
