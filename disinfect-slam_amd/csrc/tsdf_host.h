@@ -300,6 +300,9 @@ struct tsdf_engine {
   DevBuf<uint8_t> fe_mask;
   DevBuf<uint8_t> fe_out_rgb;
   DevBuf<float> fe_out_depth;
+  // distance field (tsdf_distance_field): the site bitmap, the x pass's bytes, the y pass's u16 and, for
+  // host outputs, their staging, one section each (tsdf_host_edt.hip). Grow-only.
+  DevBuf<uint8_t> edt_buf;
 
   tsdf_engine() = default;
   // D's buffers, the pinned mirrors, events and streams; the scratch above frees itself. The caller has

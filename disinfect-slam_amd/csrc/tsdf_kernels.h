@@ -351,6 +351,36 @@ __global__ void k_uv_dose(EngineDev D, DoseParams A, ViewGrid V);
 // coordinate of the ray origins of receivers some emitter irradiates (integer min / max: any order gives
 // the same box), eflag[k] = 1 for an emitter in range of a receiver. box starts at {INT_MAX x 3, INT_MIN x 3}.
 __global__ void k_dose_bounds(DoseParams A, int32_t* box, int32_t* eflag);
+// Euclidean distance field over a box (tsdf_edt.hip; DESIGN.md "Distance field"). The box, its cover by
+// whole blocks, and the site bitmap's shape: one row of rowbytes bytes (a multiple of 4, the padding zero)
+// per (z, y) of the box, byte b of a row the eight voxels of the cover's b-th block along x.
+struct EdtBox {
+  int ox, oy, oz;        // first voxel of the box
+  int nx, ny, nz;
+  int cx0, cy0, cz0;     // first block of the cover
+  int cbx, cby, cbz;     // blocks of the cover per axis
+  int rowbytes;
+  int R, min_weight, unknown;
+};
+// one workgroup of 256 per block cell of the cover: the site bits and (state != null) the state of the
+// cell's voxels inside the box. bits and state are zero before: a missing block writes neither unless
+// unknown voxels are sites.
+__global__ void k_edt_classify(EngineDev D, EdtBox B, uint8_t* bits, uint8_t* state);
+// g[z][y][x] = min(R, distance along x to the nearest site bit of the row); one thread per voxel
+__global__ void k_edt_x(EdtBox B, const uint32_t* bits, uint8_t* g);
+// out[i] = min(cap, min over |i - j| <= A of f(in[j]) + (i - j)^2) along lines of L elements `stride`
+// apart, f the square for the x pass's bytes and the identity for u16; ncol lines side by side (consecutive
+// addresses, 64 per workgroup) in each of gridDim.z slabs `slab` apart, T outputs of a line per workgroup
+// (gridDim.y = ceil(L / T)) staged with an apron of A in LDS: T + 2 A <= ROWS.
+struct EdtLine {
+  int64_t ncol, stride, slab;
+  int L, T, A;
+  uint32_t cap;
+};
+template <typename In, int ROWS, int NT>
+__global__ void k_edt_line(EdtLine P, const In* in, uint16_t* out);
+// LDS rows (128 B each) of the two forms: four workgroups of the small one share a CU's 160 KiB
+constexpr int kEdtRowsSmall = 316, kEdtRowsLarge = 768;
 // frame n's raycast (R, V: its view grid, built before) + frame n + 1's ingest (k_ingest_dda<1024>) in
 // one launch: nray raycast workgroups (rgx tiles per row) first, then kVisWorkgroups + tiles (tsdf_alloc.hip)
 __global__ void k_render_ingest(EngineDev D, FrameParams R, float step_size, ViewGrid V, uchar4* rgba,

@@ -58,6 +58,11 @@ std::vector<VoxelSpatialTSDF> DISINFSystem::query_tsdf(const BoundingCube<float>
 
 TriMesh DISINFSystem::query_mesh(const BoundingCube<float>& volumn) { return TSDF_->QueryMesh(volumn); }
 
+DistanceField DISINFSystem::query_distance_field(const BoundingCube<float>& volumn, int max_dist, int min_weight,
+                                                 bool unknown) {
+  return TSDF_->DistanceField(volumn, max_dist, min_weight, unknown);
+}
+
 void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {
   const size_t nv = mesh.verts.size() / 3;
   if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);

@@ -44,6 +44,11 @@ class DISINFSystem {
   // accumulates into mesh.dose, sized and zeroed when empty. carry_dose (uv_dose.h) moves the dose of an
   // earlier extraction over by mesh.keys.
   void irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg = nullptr);
+  // The clearance layer a lamp planner asks: squared Euclidean distances [voxels^2] from every voxel whose
+  // centre lies in `volumn` to the nearest surface voxel there, saturated at max_dist^2, with the voxels'
+  // state (TSDFGrid::DistanceField). unknown: never-observed space is an obstacle as well.
+  DistanceField query_distance_field(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
+                                     bool unknown = false);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

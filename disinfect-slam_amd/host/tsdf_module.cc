@@ -112,6 +112,14 @@ void TSDFSystem::AccumulateDose(const std::vector<float>& points, const std::vec
   tsdf_.AccumulateDose(points, normals, emitters, dose, cfg);
 }
 
+struct DistanceField TSDFSystem::DistanceField(const BoundingCube<float>& volumn, int max_dist, int min_weight,
+                                               bool unknown) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.DistanceField(volumn, max_dist, min_weight, unknown);
+}
+
 void TSDFSystem::ImportBlocks(const void* records, int64_t n, bool replace) {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });

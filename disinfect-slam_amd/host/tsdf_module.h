@@ -73,6 +73,9 @@ class TSDFSystem {
   void AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
                       const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
                       const tsdf_uv_config* cfg = nullptr);
+  // the distance field of the voxels in `volumn` (TSDFGrid::DistanceField): waits and locks like the dose calls
+  struct DistanceField DistanceField(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
+                                     bool unknown = false);
   // the volume replaced by (replace) or extended with n block records (tsdf_import_blocks, host memory;
   // one unsharded volume only), after every queued frame
   void ImportBlocks(const void* records, int64_t n, bool replace);

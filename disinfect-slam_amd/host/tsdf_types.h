@@ -230,6 +230,24 @@ struct SurfaceMaps {
   std::vector<uint8_t> rgbw;  // 4 per pixel: the hit voxel's r, g, b, fusion weight
 };
 
+// The distance field of a voxel box (tsdf_distance_field): squared Euclidean distances [voxels^2] to
+// the nearest surface voxel inside the box, saturated at max_dist^2, and the voxels' state (0 unobserved,
+// 1 observed free, 2 observed inside). Voxel (x, y, z) of the box is global voxel origin + (x, y, z).
+struct DistanceField {
+  int32_t origin[3] = {0, 0, 0};
+  int32_t dims[3] = {0, 0, 0};  // nx, ny, nz
+  int max_dist = 0;
+  std::vector<uint16_t> d2;     // nz * ny * nx, x fastest
+  std::vector<uint8_t> state;   // same shape
+  size_t at(int x, int y, int z) const { return ((size_t)z * dims[1] + y) * dims[0] + x; }
+  // the distance [voxels] at a voxel of the box: negative inside a surface
+  float signed_distance(int x, int y, int z) const {
+    const size_t i = at(x, y, z);
+    const float d = std::sqrt((float)d2[i]);
+    return state[i] == 2 ? -d : d;
+  }
+};
+
 // The pose of a depth frame against the volume (tsdf_track). degenerate: too few correspondences
 // or singular normal equations; pose is then the last good estimate (the guess when none was made).
 struct TrackResult {

@@ -179,6 +179,36 @@ void TSDFGrid::AccumulateDose(const std::vector<float>& points, const std::vecto
              "tsdf_uv_dose");
 }
 
+struct DistanceField TSDFGrid::DistanceField(const BoundingCube<float>& volumn, int max_dist, int min_weight,
+                                             bool unknown) {
+  if (group_) throw std::runtime_error("TSDFGrid::DistanceField: not available on a sharded volume");
+  const double lo[3] = {volumn.xmin, volumn.ymin, volumn.zmin}, hi[3] = {volumn.xmax, volumn.ymax, volumn.zmax};
+  struct DistanceField f;
+  tsdf_edt_config c;
+  tsdf_edt_config_default(&c);
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    const double v0 = std::ceil(lo[a] / (double)voxel_size_), v1 = std::floor(hi[a] / (double)voxel_size_);
+    if (!(v0 <= v1) || !(v0 > -1e9) || !(v1 < 1e9) || v1 - v0 >= 2048.0)
+      throw std::invalid_argument("TSDFGrid::DistanceField: the cube holds no voxel centre, or more than 2048 along an axis");
+    c.origin[a] = f.origin[a] = (int32_t)v0;
+    c.dims[a] = f.dims[a] = (int32_t)(v1 - v0) + 1;
+    n *= (size_t)c.dims[a];
+  }
+  if (n > ((size_t)1 << 28)) throw std::invalid_argument("TSDFGrid::DistanceField: more than 2^28 voxels");
+  c.max_dist = f.max_dist = max_dist;
+  c.min_weight = min_weight;
+  c.sites = TSDF_EDT_SURFACE | (unknown ? TSDF_EDT_UNKNOWN : 0);
+  f.d2.resize(n);
+  f.state.resize(n);
+  tsdf_edt_out out{};
+  out.d2 = f.d2.data();
+  out.state = f.state.data();
+  out.mem_kind = TSDF_MEM_HOST;
+  check_tsdf(tsdf_distance_field(engine_, &c, &out), "tsdf_distance_field");
+  return f;
+}
+
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {
   if (group_) throw std::runtime_error("TSDFGrid::RayCastSurface: not available on a sharded volume");
   SurfaceMaps m;

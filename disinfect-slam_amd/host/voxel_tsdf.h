@@ -58,6 +58,14 @@ class TSDFGrid {
                       const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
                       const tsdf_uv_config* cfg = nullptr);
 
+  // Exact Euclidean distance field (tsdf_distance_field) over the voxels whose centres lie in `volumn`
+  // (voxel v's centre is v * voxel_size): squared distances [voxels^2] to the nearest surface voxel of the
+  // box, saturated at max_dist^2; unknown: unobserved voxels are sites too. Pad the cube by max_dist voxels
+  // for the volume's own distances. Throws std::invalid_argument on an empty cube or one the call refuses
+  // (more than 2048 voxels along an axis or 2^28 in all). Not available on a sharded volume.
+  struct DistanceField DistanceField(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
+                                     bool unknown = false);
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

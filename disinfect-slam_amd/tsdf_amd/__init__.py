@@ -998,6 +998,46 @@ class Engine:
         _lib.check(rc, "tsdf_uv_dose")
         return d
 
+    # ---- distance field ----
+    def distance_field(self, origin, dims, max_dist: int = 255, min_weight: int = 1, unknown: bool = False,
+                       state: bool = True, device: bool = False):
+        """The exact squared Euclidean distance [voxels^2], saturated at max_dist^2, from every voxel of a
+        box to the nearest surface voxel inside the box (tsdf_distance_field). origin: the box's first
+        voxel (global voxel coordinates x, y, z), dims: (nx, ny, nz). A surface voxel is observed (its
+        block exists, weight >= min_weight), has tsdf <= 0 and a free face neighbour; with unknown=True
+        every unobserved voxel of the box is a site as well. Only sites inside the box count: pad a region
+        by max_dist. Returns dict(d2 (nz, ny, nx) uint16, state (same shape uint8: 0 unobserved, 1 free,
+        2 inside; None with state=False), origin, dims, max_dist, unknown): numpy arrays, or with
+        device=True torch tensors on this engine's GPU, ordered after the call on torch's current stream.
+        esdf.metres / esdf.signed / esdf.clearance turn the field into metres."""
+        L = _lib.load()
+        c = _lib.EdtConfig()
+        L.tsdf_edt_config_default(C.byref(c))
+        o, d = [int(v) for v in origin], [int(v) for v in dims]
+        if len(o) != 3 or len(d) != 3:
+            raise ValueError("origin and dims are three integers each")
+        c.origin, c.dims = (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d)
+        c.max_dist, c.min_weight = int(max_dist), int(min_weight)
+        c.sites = _lib.TSDF_EDT_SURFACE | (_lib.TSDF_EDT_UNKNOWN if unknown else 0)
+        # (a refused box allocates nothing: one element stands in for the outputs)
+        ok = all(1 <= v <= 2048 for v in d) and d[0] * d[1] * d[2] <= 1 << 28
+        shape = (d[2], d[1], d[0]) if ok else (1,)
+        if device:
+            import torch
+            dev = f"cuda:{self.device}"
+            d2 = torch.empty(shape, dtype=torch.uint16, device=dev)
+            st = torch.empty(shape, dtype=torch.uint8, device=dev) if state else None
+        else:
+            d2 = np.empty(shape, np.uint16)
+            st = np.empty(shape, np.uint8) if state else None
+        out = _lib.EdtOut(_ptr(d2), _ptr(st), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        outs = (d2,) if st is None else (d2, st)
+        self._wait_torch(*outs)
+        rc = L.tsdf_distance_field(self._h, C.byref(c), C.byref(out))
+        self._signal_torch(*outs)
+        _lib.check(rc, "tsdf_distance_field")
+        return dict(d2=d2, state=st, origin=tuple(o), dims=tuple(d), max_dist=int(max_dist), unknown=bool(unknown))
+
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()
         b = None if bounds is None else np.ascontiguousarray(

@@ -174,6 +174,23 @@ class UvConfig(C.Structure):
     ]
 
 
+class EdtConfig(C.Structure):
+    _fields_ = [
+        ("origin", C.c_int32 * 3),
+        ("dims", C.c_int32 * 3),
+        ("max_dist", C.c_int32),
+        ("min_weight", C.c_int32),
+        ("sites", C.c_int32),
+    ]
+
+
+class EdtOut(C.Structure):
+    _fields_ = [("d2", C.c_void_p), ("state", C.c_void_p), ("mem_kind", C.c_int)]
+
+
+TSDF_EDT_SURFACE = 1
+TSDF_EDT_UNKNOWN = 2
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -196,6 +213,7 @@ EXPORTS = [
     "tsdf_extract_mesh_indexed",
     "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track_config_default", "tsdf_track",
     "tsdf_uv_config_default", "tsdf_surface_normals", "tsdf_uv_dose",
+    "tsdf_edt_config_default", "tsdf_distance_field",
 ]
 
 _lib = None
@@ -282,6 +300,9 @@ def load(path: str | None = None):
     L.tsdf_uv_config_default.restype = None
     L.tsdf_surface_normals.argtypes = [P, P, i64, f, P, i]
     L.tsdf_uv_dose.argtypes = [P, P, P, i64, P, C.c_int32, C.POINTER(UvConfig), P, i]
+    L.tsdf_edt_config_default.argtypes = [C.POINTER(EdtConfig)]
+    L.tsdf_edt_config_default.restype = None
+    L.tsdf_distance_field.argtypes = [P, C.POINTER(EdtConfig), C.POINTER(EdtOut)]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -329,7 +350,7 @@ def load(path: str | None = None):
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
-                 "tsdf_surface_normals", "tsdf_uv_dose"):
+                 "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -1,0 +1,67 @@
+"""Helpers around Engine.distance_field (DESIGN.md "Distance field"), numpy only: the squared voxel
+distances in metres, with a sign, a box around a set of points, and the clearance at world points.
+
+A field is the dict Engine.distance_field returns (host arrays): d2 (nz, ny, nx) uint16, state (same shape,
+0 unobserved / 1 free / 2 inside, or None), origin (x, y, z), dims (nx, ny, nz), max_dist, unknown.
+
+With uv.tube_emitters a planner can reject a lamp pose before it irradiates from it: take the tube's
+emitter positions, ask clearance() for them, and drop the pose when any distance is under the threshold
+the arm needs or any state is 0 (the lamp would sit in space no frame has observed)."""
+from __future__ import annotations
+
+import numpy as np
+
+
+def metres(field, voxel: float) -> np.ndarray:
+    """sqrt(d2) * voxel as float32: the distance to the nearest site, saturated at max_dist * voxel."""
+    return (np.sqrt(np.asarray(field["d2"]).astype(np.float32)) * np.float32(voxel)).astype(np.float32)
+
+
+def signed(field, voxel: float) -> np.ndarray:
+    """metres() with a sign: negative inside (state 2), and NaN at unobserved voxels (state 0) unless the
+    field was built with unknown=True, where they are sites and read 0."""
+    if field.get("state") is None:
+        raise ValueError("signed: the field has no state (distance_field(..., state=True))")
+    d, st = metres(field, voxel), np.asarray(field["state"])
+    d = np.where(st == 2, -d, d).astype(np.float32)
+    if not field.get("unknown", False):
+        d[st == 0] = np.nan
+    return d
+
+
+def box_around(points, voxel: float, margin: float = 0.0):
+    """(origin, dims) of the voxel box that covers the (n, 3) world points [m] and `margin` metres around
+    them, as Engine.distance_field takes them. Pad by max_dist * voxel for distances that are the
+    volume's own up to the cap."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    if p.shape[0] == 0:
+        raise ValueError("box_around: no points")
+    lo = np.floor((p.min(axis=0) - margin) / voxel).astype(np.int64)
+    hi = np.ceil((p.max(axis=0) + margin) / voxel).astype(np.int64)
+    return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo + 1)
+
+
+def voxel_of(points, voxel: float, sample_offset: float = 0.0) -> np.ndarray:
+    """The library's nearest voxel of world points: round(p / voxel - sample_offset) per component in
+    float32, half away from zero, as int64 (n, 3)."""
+    f = np.asarray(points, np.float32).reshape(-1, 3) / np.float32(voxel) - np.float32(sample_offset)
+    r = np.trunc(f + np.copysign(np.float32(0.5), f))
+    r = np.where(np.abs(f) < np.float32(0.5), np.float32(0), r)
+    return np.nan_to_num(r, nan=0.0).astype(np.int64)
+
+
+def clearance(field, voxel: float, points, sample_offset: float = 0.0):
+    """(distance [m] float32 (n,), state uint8 (n,)) at the voxel nearest to each world point (voxel_of);
+    (0, 0) for a point outside the box: unknown, no clearance. Without a state array every point inside
+    the box reads state 1."""
+    v = voxel_of(points, voxel, sample_offset) - np.asarray(field["origin"], np.int64)
+    nx, ny, nz = field["dims"]
+    ok = np.all((v >= 0) & (v < np.array([nx, ny, nz])), axis=1)
+    v = np.where(ok[:, None], v, 0)
+    d2 = np.asarray(field["d2"])[v[:, 2], v[:, 1], v[:, 0]].astype(np.float32)
+    dist = np.where(ok, np.sqrt(d2) * np.float32(voxel), np.float32(0)).astype(np.float32)
+    if field.get("state") is None:
+        st = np.ones(v.shape[0], np.uint8)
+    else:
+        st = np.asarray(field["state"])[v[:, 2], v[:, 1], v[:, 0]]
+    return dist, np.where(ok, st, 0).astype(np.uint8)

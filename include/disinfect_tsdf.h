@@ -574,6 +574,48 @@ int tsdf_uv_dose(tsdf_engine* e, const float* points, const float* normals, int6
                  const tsdf_uv_emitter* emitters /* host */, int32_t m, const tsdf_uv_config* cfg /* NULL = defaults */,
                  float* dose /* n, in/out [J/m^2] */, int mem_kind /* points, normals, dose alike */);
 
+/* ---- Euclidean distance field over a box of the volume (no reference counterpart) ----
+ * The exact squared Euclidean distance, in voxels, from every voxel of a box to the nearest surface
+ * voxel of the volume -- the layer a planner asks for clearance, which the TSDF only knows inside its
+ * truncation band. All integers apart from the two float comparisons below, so the result is exact.
+ * For a voxel v (global voxel coordinates 8 * block + local):
+ *   observed(v): the block of v is allocated and the voxel's fusion weight is >= min_weight;
+ *   inside(v):   observed(v) && tsdf(v) <= 0 (the raycast's hit test, the dose's occlusion test);
+ *   free(v):     observed(v) && !inside(v);
+ *   surface(v):  inside(v) and at least one of the six face neighbours of v is free. The neighbours are
+ *                read from the volume, also when they lie outside the box: the site set of a box is the
+ *                volume's site set cut to the box and does not depend on where the box's faces fall;
+ *   site(v):     surface(v); with TSDF_EDT_UNKNOWN surface(v) || !observed(v).
+ * d2(v) = min(R * R, min over the sites s inside the box of |v - s|^2), R = max_dist; a box without
+ * sites gives R * R everywhere. Only sites inside the box count, so a voxel at least R voxels from every
+ * face of the box holds the volume's true saturated distance: a caller pads its region by R. d2 at a
+ * free voxel is the clearance, at an inside voxel the penetration depth; state gives the sign.
+ * Required: each dims[i] in 1 .. 2048, nx * ny * nz <= 2^28, every voxel of the box grown by one voxel
+ * inside the int16 block range, max_dist in 1 .. 255, min_weight >= 0, sites one of the two values, d2
+ * non-NULL; anything else is TSDF_ERR_INVALID_ARG with nothing written. The call completes a pending
+ * pipelined frame first, runs asynchronously on the engine stream for device memory and copies and
+ * synchronises for host memory, is not available on a shard engine (shard_count > 1:
+ * TSDF_ERR_INVALID_ARG), only reads the volume and sets no status bits. Its scratch (about 3 bytes per
+ * voxel, 6 for host outputs) belongs to the engine, grows on demand and is freed by tsdf_destroy. */
+#define TSDF_EDT_SURFACE 1 /* sites: surface voxels */
+#define TSDF_EDT_UNKNOWN 2 /* sites: also every unobserved voxel of the box */
+typedef struct tsdf_edt_config {
+  int32_t origin[3];  /* first voxel of the box, global voxel coordinates, x y z */
+  int32_t dims[3];    /* nx, ny, nz voxels */
+  int32_t max_dist;   /* R [voxels], 1 .. 255: distances saturate at R */
+  int32_t min_weight; /* >= 0: a voxel is observed when its block exists and its fusion weight >= this */
+  int32_t sites;      /* TSDF_EDT_SURFACE, or TSDF_EDT_SURFACE | TSDF_EDT_UNKNOWN */
+} tsdf_edt_config;
+typedef struct tsdf_edt_out {
+  uint16_t* d2;   /* nz * ny * nx, x fastest: min(R * R, squared distance [voxels^2] to the nearest site) */
+  uint8_t* state; /* same shape: 0 unobserved, 1 observed free (tsdf > 0), 2 observed inside (tsdf <= 0);
+                     NULL: skipped */
+  int mem_kind;   /* TSDF_MEM_HOST or TSDF_MEM_DEVICE, both pointers alike */
+} tsdf_edt_out;
+/* max_dist 255, min_weight 1, sites TSDF_EDT_SURFACE; origin and dims zero */
+void tsdf_edt_config_default(tsdf_edt_config* cfg);
+int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_edt_out* out);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
