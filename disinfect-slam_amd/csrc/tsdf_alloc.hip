@@ -43,7 +43,8 @@ __device__ __forceinline__ void pack_keys_wg(const EngineDev& D, ShardRec* __res
 }
 
 // grid: kVisWorkgroups sweep workgroups first (dispatched first, they overlap the tiles), then one
-// workgroup per 16x16 pixel tile (tiles_x per row, `tiles` in all). Every workgroup arrives at the
+// workgroup per pair of 16x16 pixel tiles (tiles_x tiles per row, `tiles` in all: tile_pair_wgs).
+// Every workgroup arrives at the
 // end; the last one resolves the frame's allocation (kTailResolve) or packs a shard's keys for the
 // exchange (kTailPack): block_allocate_kernel and VoxelHashTable::Allocate's launch in one.
 // wg / nwg: this workgroup among the ingest's (its own launch: the block index and the grid; the
@@ -62,17 +63,17 @@ __device__ __forceinline__ void ingest_dda(EngineDev D, FrameParams P,
     TSDF_STAMP(D, 2, 0);
     vis_sweep(D, P, wg, S);
     TSDF_STAMP(D, 2, 1);
-  } else if (wg - kVisWorkgroups < tiles) {  // tiles [P.tile_lo, P.tile_lo + tiles)
-    ingest_tile<TS, kTileFull>(D, P, depth, rgb, ht, lt, tiles_x, P.tile_lo + wg - kVisWorkgroups, S);
+  } else if (wg - kVisWorkgroups < tile_pair_wgs(tiles_x, tiles)) {  // tiles [P.tile_lo, P.tile_lo + tiles)
+    ingest_tile<TS, kTileFull>(D, P, depth, rgb, ht, lt, tiles_x, P.tile_lo, wg - kVisWorkgroups, S);
   }
-  if (!arrive_last(D.arrive + kArrIngest, 0ull, &S.last, true, (uint32_t)nwg, (uint32_t)wg)) return;
+  if (!arrive_last(D.arrive + kArrIngest, 0ull, &S.u.tail.last, true, (uint32_t)nwg, (uint32_t)wg)) return;
   const unsigned long long tend = __builtin_amdgcn_s_memrealtime();
   TSDF_STAMP(D, 6, 0);
   if (threadIdx.x == 0) arrive_reset(D.arrive + kArrIngest);  // (no loads: the resolver starts at once)
   if (P.tail == kTailPack)
     pack_keys_wg(D, P.slot, P.slot_cap);
   else
-    resolve_alloc_wg(D, P, (uint32_t)P.W * (uint32_t)P.H * (uint32_t)P.maxs, 1, S.u.res);
+    resolve_alloc_wg(D, P, (uint32_t)P.W * (uint32_t)P.H * (uint32_t)P.maxs, 1, S.u.tail.res);
   // the ingest's device span (start -> last arrival), accounted after the resolver, off its path
   TSDF_STAMP(D, 6, 1);
   if (threadIdx.x == 0) D.ctr->ingest_ticks += tend - ld_co(&D.arrive[kArrStart + 8]);

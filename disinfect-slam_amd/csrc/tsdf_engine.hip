@@ -23,11 +23,10 @@ void set_error(const char* what) { g_last_error = what; }
 // drop-in caller needs to set). Read once by tsdf_create (read_env_knobs); every other file reads
 // none. TSDF_ROCTX (roctx ranges) is read on first use by the tracing wrapper.
 //   TSDF_PIPELINE=0               unpipelined frames: two launches per frame (k_ingest_dda, k_integrate)
-//   TSDF_PIPE_MAX_PIXELS=n        largest frame (pixels) that is pipelined (default 2^19; C4 above it)
+//   TSDF_PIPE_MAX_PIXELS=n        largest frame (pixels) that is pipelined (default 2^20: C4, 1280x720, is within it)
 //   TSDF_FRAME_ORDER=0..4         k_frame grid order of its parts (PipeArgs.order; default 2)
-//   TSDF_FRAME_WG_PER_CU=n        k_frame update workgroups per CU (default kFrameUpdWgsPer2Cu / 2 = 2.5: 640)
+//   TSDF_FRAME_WG_PER_CU=n        k_frame update workgroups per CU (default kFrameUpdWgsPer4Cu / 4 = 2.75: 704)
 //   TSDF_FRAME_UPD_WGS=n          (A/B) k_frame update workgroups in total (overrides the per-CU count)
-//   TSDF_FRAME_TILES_PER_WG=n     (A/B) k_frame pixel tiles per tile workgroup (default 1)
 //   TSDF_INTEGRATE_WG_PER_CU=n    cap on k_integrate's resident workgroups per CU
 //   TSDF_CAND_CAP=n               (tests) smaller carve-candidate list, to exercise its overflow
 //   TSDF_MESH_GRID=n              (tests) fewer k_mesh workgroups, to exercise its grid stride
@@ -50,7 +49,6 @@ static EnvKnobs read_env_knobs() {
   k.pipe_max_pixels = num("TSDF_PIPE_MAX_PIXELS", -1);
   k.frame_order = (int)std::max(-1ll, num("TSDF_FRAME_ORDER", -1));
   k.frame_wg_per_cu = (int)num("TSDF_FRAME_WG_PER_CU", 0);
-  k.frame_tiles_per_wg = (int)std::max(1ll, num("TSDF_FRAME_TILES_PER_WG", 1));
   k.frame_upd_wgs = (int)num("TSDF_FRAME_UPD_WGS", 0);
   k.integrate_wg_per_cu = (int)num("TSDF_INTEGRATE_WG_PER_CU", 0);
   k.cand_cap = (int)num("TSDF_CAND_CAP", 0);
@@ -336,13 +334,16 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pre, reinterpret_cast<const void*>(k_frame),
                                                      kIntegrateThreads, 0) != hipSuccess)
       return fail(TSDF_ERR_HIP);
-    // 2.5 update workgroups per CU by default (of 6 that fit): the other slots take the sweep's and
-    // the tiles' workgroups from the start. Round 6, final build (exact semantic chain, 6 waves per
+    // 2.75 update workgroups per CU by default (of 6 that fit): the other slots take the sweep's and
+    // the tile pairs' workgroups from the start. Round 7 (tile pairs, 600 tile workgroups at 640x480;
+    // same box, interleaved, driver command / 300 frames): 704 21.21-21.26k / 24.86-25.01k frames/s,
+    // 640 20.69-20.91k / 24.42-24.68k, 608 20.39-20.55k / 24.40-24.48k (the parent, 1,200 tile workgroups
+    // and 640: 20.93-21.13k / 23.29-23.52k; profiles/ab/r7_tile_pairs_ab.txt). Round 6, final build (exact semantic chain, 6 waves per
     // SIMD, no packed fp32): 640 update workgroups 20.94-20.99k frames/s on the driver command, 704
     // 20.8-21.0k, 768 20.6k, 896 20.2k (profiles/ab/r6_upd_wgs_nopk_ab.txt); with packed fp32 768 was
     // ahead (19.6k vs 18.7-19.4k at 640). Round 5 (log-odds state, 7 waves): 640 23.9k, 768
     // 23.3-23.5k, 512 23.4-23.7k; earlier rounds: 4 per CU 22.0-22.5k, 5 21.0-21.3k, 7 18.5-18.7k
-    int upd = kFrameUpdWgsPer2Cu * ncu / 2;
+    int upd = kFrameUpdWgsPer4Cu * ncu / 4;
     if (e->env.frame_wg_per_cu > 0) upd = e->env.frame_wg_per_cu * ncu;
     if (e->env.frame_upd_wgs > 0) upd = e->env.frame_upd_wgs;
     D.integrate_grid_pre = std::max(8, std::min({kIntegrateGrid, upd, per_cu_pre * ncu}) & ~7);

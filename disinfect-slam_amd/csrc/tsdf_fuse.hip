@@ -1028,7 +1028,7 @@ __device__ __forceinline__ void pipe_head(const EngineDev& D, const FrameParams&
     drain_barrier();
     publish_flags(D.pipe + kPipeCarved, A.tag);
     TSDF_STAMP_WG(D, 8, 0, 3);
-    if (A.has_alloc) resolve_alloc_wg(D, Pu, A.range, 1, U.ing.u.res);
+    if (A.has_alloc) resolve_alloc_wg(D, Pu, A.range, 1, U.ing.u.tail.res);
   }
   drain_barrier();
   const unsigned long long t_pub = __builtin_amdgcn_s_memrealtime();
@@ -1366,15 +1366,10 @@ __device__ __forceinline__ int frame_part(const EngineDev& D, const FrameParams&
   if (TSDF_PRIO_TILE) __builtin_amdgcn_s_setprio(TSDF_PRIO_TILE);
   const unsigned long long* aflag = D.pipe + kPipeAlloc + (blockIdx.x & 7) * 16;
   if (part == 1) {
-    // tiles_per_wg consecutive tiles per workgroup (TSDF_FRAME_TILES_PER_WG; 1 shipped): with 2 every
-    // tile workgroup is resident beside the update from the start, but its tiles run one after the
-    // other -- driver 22.2k frames/s against 23.2k at 1 (3: 20.4k, 4: 18.1k; same box)
-    const int t0 = o * A.tiles_per_wg, t1 = min(A.tiles, t0 + A.tiles_per_wg);
-    for (int t = t0; t < t1; ++t) {
-      if (t != t0) __syncthreads();  // (the previous tile's probes read the LDS key set)
-      ingest_tile<1024, kTileChained>(D, Pn, Pn.depth, Pn.rgb, Pn.ht, Pn.lt, A.tiles_x, t, U.ing, aflag, A.tag,
-                                      A.fid_new);
-    }
+    // one pair of tiles per workgroup, its two tiles' round trips overlapped (ingest_tile), so every tile
+    // workgroup is resident beside the update from the start
+    ingest_tile<1024, kTileChained>(D, Pn, Pn.depth, Pn.rgb, Pn.ht, Pn.lt, A.tiles_x, 0, o, U.ing, aflag, A.tag,
+                                    A.fid_new);
   } else
     vis_sweep_chained<1024>(frame_view(D, A.fid_new), Pn, o, U.ing, aflag, A.tag);
   if (threadIdx.x == 0)  // the ingest's span ends with its last workgroup

@@ -143,7 +143,7 @@ struct EnvKnobs {
   bool pipeline = true;
   int64_t pipe_max_pixels = -1;
   int frame_order = -1, frame_wg_per_cu = 0, integrate_wg_per_cu = 0, cand_cap = 0, mesh_grid = 0;
-  int frame_tiles_per_wg = 1, frame_upd_wgs = 0;
+  int frame_upd_wgs = 0;
   bool render_overlap = false, graph_memcpy_node = false;
   int upload_streams = 2;
   bool fuse_view_grid = true;
@@ -280,7 +280,7 @@ struct tsdf_engine {
   // allocation and update are pending (p_fid's tiles probed and inserted its keys, its sweep listed
   // its blocks). Every other entry point first completes them (flush_pending).
   bool pipeline = true;
-  int64_t pipe_max_pixels = (int64_t)1 << 19;  // larger frames take two launches (pipe_frame_size)
+  int64_t pipe_max_pixels = (int64_t)1 << 20;  // larger frames take two launches (pipe_frame_size)
   static constexpr int kPipeNone = 0, kPipeU = 1, kPipeCAU = 2, kPipeAU = 3, kPipeC = 4;  // kPipeAU:
   // p_fid's allocation and update are pending with no carving (after a graph frame that started a
   // stream); kPipeC: only p_fid's carving is pending (a shard's pipelined frames, between flush steps)

@@ -140,7 +140,7 @@ static int frame_ingest(tsdf_engine* e, const EngineDev& Dv, const tsdf_frame* f
     e->rd.pending = false;
     const tsdf_engine::DeferredRender& r = e->rd;
     const int rgx = (r.P.W + 15) / 16, nray = rgx * ((r.P.nrows + 15) / 16);
-    hipLaunchKernelGGL(k_render_ingest, dim3(nray + kVisWorkgroups + tiles), dim3(256), 0, s, Dv, r.P, r.step, r.V,
+    hipLaunchKernelGGL(k_render_ingest, dim3(nray + kVisWorkgroups + tile_pair_wgs(tiles_x, tiles)), dim3(256), 0, s, Dv, r.P, r.step, r.V,
                        r.rgba, r.normal, rgx, nray, *P, depth, rgb, ht, lt, tiles_x, tiles);
     LAUNCH_OK("k_render_ingest");
     return TSDF_OK;
@@ -151,10 +151,10 @@ static int frame_ingest(tsdf_engine* e, const EngineDev& Dv, const tsdf_frame* f
     if (rc) return rc;
   }
   if (e->maxs <= 3)
-    hipLaunchKernelGGL(k_ingest_dda<1024>, dim3(kVisWorkgroups + tiles), dim3(256), 0, s, Dv, *P, depth,
+    hipLaunchKernelGGL(k_ingest_dda<1024>, dim3(kVisWorkgroups + tile_pair_wgs(tiles_x, tiles)), dim3(256), 0, s, Dv, *P, depth,
                        rgb, ht, lt, tiles_x, tiles);
   else
-    hipLaunchKernelGGL(k_ingest_dda<2048>, dim3(kVisWorkgroups + tiles), dim3(256), 0, s, Dv, *P, depth,
+    hipLaunchKernelGGL(k_ingest_dda<2048>, dim3(kVisWorkgroups + tile_pair_wgs(tiles_x, tiles)), dim3(256), 0, s, Dv, *P, depth,
                        rgb, ht, lt, tiles_x, tiles);
   LAUNCH_OK("k_ingest_dda");
   return TSDF_OK;
@@ -199,8 +199,7 @@ void finish_args(tsdf_engine* e, PipeArgs& A, const FrameParams& Pu) {
   A.order = e->frame_order;
   A.range = A.has_alloc ? (uint32_t)((size_t)Pu.W * Pu.H * e->maxs) : 0u;
   if (!A.has_frame) A.tiles = A.tiles_x = 0;
-  A.tiles_per_wg = std::max(1, e->env.frame_tiles_per_wg);
-  A.tile_wgs = (A.tiles + A.tiles_per_wg - 1) / A.tiles_per_wg;
+  A.tile_wgs = tile_pair_wgs(A.tiles_x, A.tiles);
 }
 
 // One k_frame launch (tsdf_fuse.hip): frame A.fid_carve's carving, frame A.fid_alloc's allocation and
@@ -229,10 +228,12 @@ static int launch_frame(tsdf_engine* e, PipeArgs A, const FrameParams& Pu, const
   return TSDF_OK;
 }
 
-// Frames up to pipe_max_pixels (2^19; TSDF_PIPE_MAX_PIXELS) are pipelined (k_frame). Larger frames take the two launches: their
-// ingest (3,600 tiles at 1280x720) no longer fits beside the update in one launch's resident
-// workgroups, and the serialised launch is slower (C4, driver-size runs: 13.0-13.3k frames/s
-// pipelined against 14.6-14.8k in two launches; at 640x480 21.4k against 19.1k).
+// Frames up to pipe_max_pixels (2^20; TSDF_PIPE_MAX_PIXELS) are pipelined (k_frame). Larger frames take the two
+// launches. With one workgroup per 16x16 tile the gate stood at 2^19: a 1280x720 frame's 3,600 tile workgroups
+// did not fit beside the update (C4, driver-size runs: 13.0-13.3k frames/s pipelined against 14.6-14.8k in two
+// launches). With tile pairs (1,800 workgroups) the pipelined form is ahead at both lengths (same box,
+// interleaved: 17.6-17.8k against 14.4k at the driver's length, 19.4-19.5k against 15.9k over 300 frames;
+// profiles/ab/r7_c4_gate_ab.txt); nothing larger has been measured.
 bool pipe_frame_size(const tsdf_engine* e, int w, int h) { return (int64_t)w * h <= e->pipe_max_pixels; }
 
 // The k_frame launch that continues the pending frames, with (has_frame) the ingest of a new frame
@@ -561,7 +562,7 @@ static int shard_pipe_impl(tsdf_engine* e, const tsdf_frame* f, const tsdf_intri
     const EngineDev Dv = frame_view(e->D, fid);
     const int tiles = P.tile_hi - P.tile_lo, tiles_x = (P.W + 15) / 16;
     HIP_OK(hipMemsetAsync(&e->D.ctr->n_pend, 0, sizeof(int32_t), e->stream));  // (its allocation's list)
-    hipLaunchKernelGGL(k_ingest_dda<1024>, dim3(kVisWorkgroups + tiles), dim3(256), 0, e->stream, Dv, P, P.depth,
+    hipLaunchKernelGGL(k_ingest_dda<1024>, dim3(kVisWorkgroups + tile_pair_wgs(tiles_x, tiles)), dim3(256), 0, e->stream, Dv, P, P.depth,
                        P.rgb, P.ht, P.lt, tiles_x, tiles);
     LAUNCH_OK("k_ingest_dda");
     if (dsts_host) {  // (no candidates from this call)

@@ -100,24 +100,24 @@ int graph_create(tsdf_engine* e, int width, int height, int render_width, int re
   if ((err = hipHostMalloc(&g->h_args, sizeof(FrameArgs) * nargs)) != hipSuccess)
     return fail(err, "graph host args");
   std::memset(g->h_args, 0, sizeof(FrameArgs) * nargs);
-  const int tiles = ((width + 15) / 16) * ((height + 15) / 16);
+  const int tiles_x = (width + 15) / 16;
+  const int tile_wgs = tile_pair_wgs(tiles_x, tiles_x * ((height + 15) / 16));
   // the engine's queued work must be done before the capture stream records anything
   if ((err = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(err, "graph sync");
   // the nodes of one frame (args entry A)
   auto frame_nodes = [&](const FrameArgs* A) {
     if (g->pipe) {  // one k_frame per frame, its grid sized for the largest launch (steady state)
-      const int tpw = std::max(1, e->env.frame_tiles_per_wg);
-      const int nwg = kPipeHead + kPipeFreshWG + e->D.integrate_grid_pre + (tiles + tpw - 1) / tpw + kVisWorkgroups;
+      const int nwg = kPipeHead + kPipeFreshWG + e->D.integrate_grid_pre + tile_wgs + kVisWorkgroups;
       hipLaunchKernelGGL(k_frame_g, dim3(nwg), dim3(kIntegrateThreads), 0, g->cap, e->D, A);
     } else {
       const int rgx = (render_width + 15) / 16, nray = rgx * ((render_height + 15) / 16);
       if (g->defer)  // the previous frame's raycast (args->prev; none: its workgroups exit) + this ingest
-        hipLaunchKernelGGL(k_render_ingest_g, dim3(nray + kVisWorkgroups + tiles), dim3(256), 0, g->cap, e->D,
+        hipLaunchKernelGGL(k_render_ingest_g, dim3(nray + kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D,
                            A, rgx, nray);
       else if (e->maxs <= 3)
-        hipLaunchKernelGGL(k_ingest_dda_g<1024>, dim3(kVisWorkgroups + tiles), dim3(256), 0, g->cap, e->D, A);
+        hipLaunchKernelGGL(k_ingest_dda_g<1024>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
       else
-        hipLaunchKernelGGL(k_ingest_dda_g<2048>, dim3(kVisWorkgroups + tiles), dim3(256), 0, g->cap, e->D, A);
+        hipLaunchKernelGGL(k_ingest_dda_g<2048>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
       if (render_width && e->env.fuse_view_grid)  // the render camera's view grid built in the update launch
         hipLaunchKernelGGL(k_integrate_vg_g, dim3(e->D.integrate_grid + kOccWords / 256), dim3(kIntegrateThreads), 0,
                            g->cap, e->D, A, e->D.integrate_grid);
@@ -228,7 +228,8 @@ int tsdf_graph_create_shard(tsdf_engine* e, int width, int height, int slice_ind
   std::memset(g->h_args, 0, sizeof(FrameArgs) * tsdf_graph::kSlots);
   const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
   const int rows = (tiles_y + slice_count - 1) / slice_count;
-  const int tiles = (std::min(tiles_y, (slice_index + 1) * rows) - std::min(tiles_y, slice_index * rows)) * tiles_x;
+  const int tile_wgs = tile_pair_wgs(
+      tiles_x, (std::min(tiles_y, (slice_index + 1) * rows) - std::min(tiles_y, slice_index * rows)) * tiles_x);
   if ((err = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(err, "graph sync");
   for (int k = 0; k < tsdf_graph::kSlots; ++k) {
     const FrameArgs* A = g->d_args + k;
@@ -240,9 +241,9 @@ int tsdf_graph_create_shard(tsdf_engine* e, int width, int height, int slice_ind
         hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(64), 0, g->cap, reinterpret_cast<uint32_t*>(g->d_args + k),
                            reinterpret_cast<const uint32_t*>(g->h_args + k), (int)(sizeof(FrameArgs) / 4));
         if (e->maxs <= 3)
-          hipLaunchKernelGGL(k_ingest_dda_g<1024>, dim3(kVisWorkgroups + tiles), dim3(256), 0, g->cap, e->D, A);
+          hipLaunchKernelGGL(k_ingest_dda_g<1024>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
         else
-          hipLaunchKernelGGL(k_ingest_dda_g<2048>, dim3(kVisWorkgroups + tiles), dim3(256), 0, g->cap, e->D, A);
+          hipLaunchKernelGGL(k_ingest_dda_g<2048>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
       } else if (seg == 1) {
         if (slice_count > 1)
           hipLaunchKernelGGL(k_resolve_alloc_g, dim3(1), dim3(kRT), 0, g->cap, e->D, A);

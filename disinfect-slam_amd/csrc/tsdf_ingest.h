@@ -12,14 +12,14 @@
 namespace tsdf {
 
 // ---------------------------------------------------------------------------------------------
-// k_ingest_dda: 16x16 pixel tile per workgroup.
+// k_ingest_dda: a pair of horizontally adjacent 16x16 pixel tiles per workgroup, two pixels per thread.
 //  1. pack the frame into per-pixel records the integrate kernel gathers (one 16-B gather per voxel):
 //       pixA = {depth, +-range (range = |K^-1 [x y 1]|; negative: the pixel takes the semantic update's
 //       exact path, sem_pixel_fast), logf(ht), logf(lt)} (sem_logf), pixC = rgb
 //     (exactly the values tsdf_integrate_kernel recomputes per voxel, voxel_tsdf.cu:174-201; the
 //     update computes w_new = (1 - d / max_depth) * 4 from the depth with the same operations)
 //  2. DDA of [p - trunc dir, p + trunc dir] (voxel_tsdf.cu:116-146); block keys deduplicated in
-//     an LDS hash set with their smallest candidate order (y*W + x)*maxs + i
+//     the pair's LDS hash set with their smallest candidate order (y*W + x)*maxs + i
 //  3. each unique key once: all-8-corners visibility (is_block_visible<true>), table probe;
 //     missing keys go to the global new-key set.
 // The launch covers tiles [P.tile_lo, P.tile_hi): every tile of the frame, or a sharded frame's
@@ -28,9 +28,10 @@ namespace tsdf {
 // copy of the whole hash index, so its keys are exactly the ones one volume's DDA finds in those
 // tiles, whichever shard owns them.
 // ---------------------------------------------------------------------------------------------
-// LDS key-set slots per 16x16 tile: TS > 256 pixels x maxs. 1024 for maxs <= 3 (the reference's
-// 6x truncation / voxel ratio: 2-3 samples per pixel) keeps the workgroup at 16.5 KiB of LDS, so 9
-// workgroups fit a CU and the whole 640x480 grid is resident at once; 2048 up to maxs = 6.
+// LDS key-set slots per 16x16 tile: TS > 256 pixels x maxs, so a pair's 2 TS one-word slots hold its
+// worst case (every sample a key of its own) and an insert always finds a slot. 1024 for maxs <= 3
+// (the reference's 6x truncation / voxel ratio: 2-3 samples per pixel): 16 KiB of slots, under the
+// sweep's 16.5 KiB, so 9 workgroups fit a CU; 2048 up to maxs = 6 (32 KiB, 5 workgroups per CU).
 constexpr int kVisChunk = 1024;   // visibility sweep: 16 occupancy words x 64 entries per wave
 static_assert(kBands == 16, "ResolveLds band arrays");
 
@@ -58,9 +59,7 @@ template <int TS>
 struct IngestLds {
   union {
     struct {
-      unsigned long long key[TS];
-      uint32_t ord[TS];
-      uint16_t vis[4][TS / 4];
+      unsigned long long slot[2 * TS];  // the tile pair's key set (ingest_tile)
     } tile;
     struct {
       uint32_t list[4][kVisChunk];
@@ -68,9 +67,11 @@ struct IngestLds {
       int npass;
       unsigned long long dm[4];  // (vis_sweep_chained) the carving's marks of each wave's 64 words
     } sweep;
-    AllocLdsT<kIngestRB> res;  // the last-arriving workgroup's allocation resolve
+    struct {
+      AllocLdsT<kIngestRB> res;  // the last-arriving workgroup's allocation resolve
+      int last;                  // its arrival flag (written after the tiles and the sweep are done)
+    } tail;
   } u;
-  int last;
 };
 
 // the workgroup waits until *flag == tag (thread 0 polls; bounded: a flag that never comes sets
@@ -429,15 +430,22 @@ __device__ __forceinline__ void vis_sweep_chained(const EngineDev& D, const Fram
   }
 }
 
-// One 16x16 pixel tile. kTileFull: k_ingest_dda's tile -- pixel records, the DDA, the LDS key dedupe,
-// the all-corners test, then the table probe and the new-key insert. kTileChained: the same tile of
-// frame c inside a pipelined launch (k_frame): everything that reads only the frame and its camera runs
-// while frame c - 1's blocks are updated; the probe and insert wait until frame c - 1's allocation has
-// been published (*flag == tag) and read the table coherently (the allocation ran on another XCD). Frame
-// c - 2's carving has not run yet (it runs in the next launch), so a key found now may be missing after
-// it: a found key records its smallest candidate order in D.fo at its hash entry, tagged ~fid, and the
-// carving re-inserts the keys it deletes (tsdf_resolve.h carved_key). Missing keys stay missing (a
-// carving only deletes), so they go to the new-key set now.
+// One pair of horizontally adjacent 16x16 pixel tiles of a tile row (the row's last workgroup has one
+// tile when tiles_x is odd: the right half's pixels are then outside the image, like those of a partial
+// tile). Thread t owns pixel (x, y) of the left tile and (x + 16, y) of the right, and every phase
+// handles both before it waits: the frame loads of both pixels are issued together, the DDA advances
+// both rays per step, and the corner tests, probes and inserts run over the pair's one key set -- the
+// tile's chain of dependent round trips is paid once for two tiles, half as many workgroups cover the
+// frame (so a pipelined frame's are resident beside the update from the start), and a key both tiles
+// see is tested, probed and tagged once. kTileFull: k_ingest_dda's tiles -- pixel records, the DDA, the
+// LDS key dedupe, the all-corners test, then the table probe and the new-key insert. kTileChained: the
+// same tiles of frame c inside a pipelined launch (k_frame): everything that reads only the frame and
+// its camera runs while frame c - 1's blocks are updated; the probe and insert wait until frame c - 1's
+// allocation has been published (*flag == tag) and read the table coherently (the allocation ran on
+// another XCD). Frame c - 2's carving has not run yet (it runs in the next launch), so a key found now
+// may be missing after it: a found key records its smallest candidate order in D.fo at its hash entry,
+// tagged ~fid, and the carving re-inserts the keys it deletes (tsdf_resolve.h carved_key). Missing keys
+// stay missing (a carving only deletes), so they go to the new-key set now.
 constexpr int kTileFull = 0, kTileChained = 1;
 #ifdef TSDF_CHAIN_PLAIN
 constexpr bool kChainCoherentLoads = false;
@@ -445,174 +453,239 @@ constexpr bool kChainCoherentLoads = false;
 constexpr bool kChainCoherentLoads = true;
 #endif
 
+// A slot of the pair's key set is one word: the block key (pack_key: 49 bits) above the sample's
+// pair-local candidate order ((ly * 32 + lx) * maxs + s < 512 * 6), 0 when empty. The local order is
+// monotone in the candidate order (y * W + x) * maxs + s among the pair's samples, so the smallest word
+// of a key carries its smallest order, which the probes rebuild from the pair's origin.
+constexpr int kSlotOrdBits = 15;
+static_assert(512 * kMaxDdaSamples <= (1 << kSlotOrdBits), "pair-local candidate order");
+
+// one pixel of the pair as loaded from the frame
+struct TilePix {
+  float d, h, l;
+  uint32_t c;
+};
+__device__ __forceinline__ TilePix tile_pix_load(const FrameParams& P, const float* __restrict__ depth,
+                                                 const uint8_t* __restrict__ rgb, const float* __restrict__ ht,
+                                                 const float* __restrict__ lt, bool in, int i) {
+  TilePix q{0.0f, 1.0f, 1.0f, 0u};
+  if (in) {
+    q.d = depth[i];
+    if (P.pack_pixels) {  // (a shard's k_integrate reads the raw frame instead)
+      q.c = (uint32_t)rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) | ((uint32_t)rgb[3 * i + 2] << 16);
+      if (ht) q.h = ht[i];
+      if (lt) q.l = lt[i];
+    }
+  }
+  return q;
+}
+// DDA state of a pixel's ray (nsamp > 0: a pixel of this slice with 0 < d <= max_depth)
+struct TileRay {
+  f3 pos, st;
+  int nsamp;
+};
+// the pixel's record (P.pack_pixels) and its ray
+__device__ __forceinline__ TileRay tile_pix_ray(const EngineDev& D, const FrameParams& P, bool in, int x, int y,
+                                                const TilePix& q) {
+  TileRay r{};
+  if (!in) return r;
+  const int i = y * P.W + x;
+  const float d = q.d;
+  const f3 pc = pixel_ray(P, x, y);
+  const float range = sqrtf(dot3(pc, pc));  // img_depth_to_range (voxel_tsdf.cu:120)
+  if (P.pack_pixels) {
+    // the range's sign carries sem_pixel_fast (range >= 1): negative = the update's exact path
+    D.pixA[P.pix_off + i] = make_float4(d, sem_pixel_fast(q.h, q.l, d, P.max_depth) ? range : -range,
+                                        sem_logf(q.h), sem_logf(q.l));
+    D.pixC[P.pix_off + i] = q.c;
+  }
+  if (d == 0 || d > P.max_depth) return r;
+  const f3 pcd = {pc.x * d, pc.y * d, pc.z * d};
+  const f3 pw = se3_apply(P.wq, P.wt, pcd);
+  // pc / range (IEEE quotients; pc.z = 1): the Newton-refined pair division, exact in range
+  const float rr = __builtin_amdgcn_rcpf(range);
+  const v2f dxy = div_pair(v2(pc.x, pc.y), v2(range, range), v2(rr, rr), true, true);
+  const v2f dz1 = div_pair(v2(pc.z, pc.z), v2(range, range), v2(rr, rr), true, false);
+  const f3 dc = {dxy.x, dxy.y, dz1.x};
+  const f3 dw = qrot(P.wq, dc);
+  const f3 sw = {pw.x - dw.x * P.trunc, pw.y - dw.y * P.trunc, pw.z - dw.z * P.trunc};
+  const f3 dg = {quot_const(dw.x, P.voxel, P.inv_voxel), quot_const(dw.y, P.voxel, P.inv_voxel),
+                 quot_const(dw.z, P.voxel, P.inv_voxel)};
+  const f3 sg = {quot_const(sw.x, P.voxel, P.inv_voxel), quot_const(sw.y, P.voxel, P.inv_voxel),
+                 quot_const(sw.z, P.voxel, P.inv_voxel)};
+  const float two_trunc = 2 * P.trunc;
+  const f3 rg = {two_trunc * dg.x, two_trunc * dg.y, two_trunc * dg.z};
+  const int step_grid = f2i(ceilf(fmaxf(fmaxf(fabsf(rg.x), fabsf(rg.y)), fabsf(rg.z)) / kBlockLen));
+  const float div = fmaxf((float)step_grid, 1.0f);
+  // ray / max(step_grid, 1): step_grid is 1 or 2 at the reference's 6x truncation / voxel
+  // ratio, where the quotient is exact as a product; larger counts take the IEEE divide
+  if (__builtin_expect(div <= 2.0f, 1)) {
+    const float m = div == 2.0f ? 0.5f : 1.0f;
+    r.st = {rg.x * m, rg.y * m, rg.z * m};
+  } else {
+    r.st = {rg.x / div, rg.y / div, rg.z / div};
+  }
+  r.pos = sg;
+  r.nsamp = step_grid + 1;
+  if (r.nsamp > P.maxs) {
+    atomicOr(&D.ctr->status, 4u);  // TSDF_STATUS_DDA_OVERFLOW
+    r.nsamp = P.maxs;
+  }
+  return r;
+}
+// sample s of a ray: its block key (0 past the ray's samples); the ray advances
+__device__ __forceinline__ unsigned long long tile_ray_key(TileRay& r, int s) {
+  if (s >= r.nsamp) return 0ull;
+  const int16_t kx = (int16_t)(round_s16(r.pos.x) >> kBlockLenBits);
+  const int16_t ky = (int16_t)(round_s16(r.pos.y) >> kBlockLenBits);
+  const int16_t kz = (int16_t)(round_s16(r.pos.z) >> kBlockLenBits);
+  r.pos.x += r.st.x;
+  r.pos.y += r.st.y;
+  r.pos.z += r.st.z;
+  return pack_key(kx, ky, kz);
+}
+__device__ __forceinline__ unsigned long long shfl_up64(unsigned long long v, int d) {
+  return ((unsigned long long)__shfl_up((uint32_t)(v >> 32), d, 64) << 32) | __shfl_up((uint32_t)v, d, 64);
+}
+
+// pair: the workgroup's pair among those of the tile rows from tile0's (tile0: the first tile of the
+// launch's slice, a multiple of tiles_x); PS = 2 TS slots hold the pair's 512 pixels x maxs samples
 template <int TS, int Mode = kTileFull>
 __device__ __forceinline__ void ingest_tile(const EngineDev& D, const FrameParams& P,
                                             const float* __restrict__ depth,
                                             const uint8_t* __restrict__ rgb,
                                             const float* __restrict__ ht,
-                                            const float* __restrict__ lt, int tiles_x, int tile,
+                                            const float* __restrict__ lt, int tiles_x, int tile0, int pair,
                                             IngestLds<TS>& S, const unsigned long long* flag = nullptr,
                                             uint32_t tag = 0u, uint32_t fid = 0u) {
-  unsigned long long* s_key = S.u.tile.key;
-  uint32_t* s_ord = S.u.tile.ord;
+  constexpr int PS = 2 * TS;
+  unsigned long long* s_slot = S.u.tile.slot;
   TSDF_STAMP(D, 0, 0);
-  for (int i = threadIdx.x; i < TS; i += 256) {
-    s_key[i] = 0ull;
-    s_ord[i] = 0xFFFFFFFFu;
-  }
+  for (int i = threadIdx.x; i < PS; i += 256) s_slot[i] = 0ull;
   __syncthreads();
   TSDF_STAMP(D, 0, 1);
-  const int x = (tile % tiles_x) * 16 + (threadIdx.x & 15);
-  const int y = (tile / tiles_x) * 16 + (threadIdx.x >> 4);
-  // DDA state of this lane's ray (valid: a pixel of this slice with 0 < d <= max_depth)
-  bool ray = false;
-  int nsamp = 0;
-  f3 pos{}, st{};
-  uint32_t order0 = 0;
-  if (x < P.W && y < P.H) {
-    const int i = y * P.W + x;
-    const float d = depth[i];
-    const f3 pc = pixel_ray(P, x, y);
-    const float range = sqrtf(dot3(pc, pc));  // img_depth_to_range (voxel_tsdf.cu:120)
-    if (P.pack_pixels) {  // (a shard's k_integrate reads the raw frame instead)
-      const uint32_t c = (uint32_t)rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) |
-                         ((uint32_t)rgb[3 * i + 2] << 16);
-      const float h = ht ? ht[i] : 1.0f;
-      const float l = lt ? lt[i] : 1.0f;
-      // the range's sign carries sem_pixel_fast (range >= 1): negative = the update's exact path
-      D.pixA[P.pix_off + i] = make_float4(d, sem_pixel_fast(h, l, d, P.max_depth) ? range : -range,
-                                          sem_logf(h), sem_logf(l));
-      D.pixC[P.pix_off + i] = c;
-    }
-    TSDF_STAMP(D, 0, 2);
-    if (!(d == 0 || d > P.max_depth)) {
-      const f3 pcd = {pc.x * d, pc.y * d, pc.z * d};
-      const f3 pw = se3_apply(P.wq, P.wt, pcd);
-      // pc / range (IEEE quotients; pc.z = 1): the Newton-refined pair division, exact in range
-      const float rr = __builtin_amdgcn_rcpf(range);
-      const v2f dxy = div_pair(v2(pc.x, pc.y), v2(range, range), v2(rr, rr), true, true);
-      const v2f dz1 = div_pair(v2(pc.z, pc.z), v2(range, range), v2(rr, rr), true, false);
-      const f3 dc = {dxy.x, dxy.y, dz1.x};
-      const f3 dw = qrot(P.wq, dc);
-      const f3 sw = {pw.x - dw.x * P.trunc, pw.y - dw.y * P.trunc, pw.z - dw.z * P.trunc};
-      const f3 dg = {quot_const(dw.x, P.voxel, P.inv_voxel), quot_const(dw.y, P.voxel, P.inv_voxel),
-                     quot_const(dw.z, P.voxel, P.inv_voxel)};
-      const f3 sg = {quot_const(sw.x, P.voxel, P.inv_voxel), quot_const(sw.y, P.voxel, P.inv_voxel),
-                     quot_const(sw.z, P.voxel, P.inv_voxel)};
-      const float two_trunc = 2 * P.trunc;
-      const f3 rg = {two_trunc * dg.x, two_trunc * dg.y, two_trunc * dg.z};
-      const int step_grid =
-          f2i(ceilf(fmaxf(fmaxf(fabsf(rg.x), fabsf(rg.y)), fabsf(rg.z)) / kBlockLen));
-      const float div = fmaxf((float)step_grid, 1.0f);
-      // ray / max(step_grid, 1): step_grid is 1 or 2 at the reference's 6x truncation / voxel
-      // ratio, where the quotient is exact as a product; larger counts take the IEEE divide
-      if (__builtin_expect(div <= 2.0f, 1)) {
-        const float m = div == 2.0f ? 0.5f : 1.0f;
-        st = {rg.x * m, rg.y * m, rg.z * m};
-      } else {
-        st = {rg.x / div, rg.y / div, rg.z / div};
-      }
-      pos = sg;
-      ray = true;
-      nsamp = step_grid + 1;
-      if (nsamp > P.maxs) {
-        atomicOr(&D.ctr->status, 4u);  // TSDF_STATUS_DDA_OVERFLOW
-        nsamp = P.maxs;
-      }
-      order0 = (uint32_t)i * (uint32_t)P.maxs;
-    }
-  }
-  // Samples s = 0 .. step_grid of every ray (voxel_tsdf.cu:141-146) into the tile's LDS key set
+  const int pairs_x = (tiles_x + 1) >> 1;
+  const int prow = pair / pairs_x;
+  const int x0 = (pair - prow * pairs_x) * 32, y0 = (tile0 / tiles_x + prow) * 16;
+  const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+  const int x = x0 + lx, y = y0 + ly;
+  // the pair's two pixels of this lane: both loaded, then both records and rays
+  const bool in0 = x < P.W && y < P.H, in1 = x + 16 < P.W && y < P.H;
+  const TilePix q0 = tile_pix_load(P, depth, rgb, ht, lt, in0, y * P.W + x);
+  const TilePix q1 = tile_pix_load(P, depth, rgb, ht, lt, in1, y * P.W + x + 16);
+  TileRay r0 = tile_pix_ray(D, P, in0, x, y, q0);
+  TileRay r1 = tile_pix_ray(D, P, in1, x + 16, y, q1);
+  TSDF_STAMP(D, 0, 2);
+  // Samples s = 0 .. step_grid of every ray (voxel_tsdf.cu:141-146) into the pair's LDS key set
   // with their smallest candidate order. Neighbouring pixels mostly hit the same blocks, so a sample
   // whose key equals the key of the same step at the pixel to its left or above (a lane 1 or 16
-  // lower: the wave's 16x4 pixels are in raster order), or of the previous step at this pixel, is
-  // left out -- that sample has a smaller candidate order, and by induction some sample with the
-  // key and an order no larger is inserted. That removes most same-key LDS atomics (the serialised
-  // bank conflicts of r2's profile: 1.3 conflict cycles per LDS instruction cycle).
-  unsigned long long prev_key = 0ull;
-  for (int s = 0; s < P.maxs; ++s) {
-    const bool on = ray && s < nsamp;  // (uniform loop; the shuffles need every lane)
-    unsigned long long key = 0ull;
-    if (on) {
-      const int16_t kx = (int16_t)(round_s16(pos.x) >> kBlockLenBits);
-      const int16_t ky = (int16_t)(round_s16(pos.y) >> kBlockLenBits);
-      const int16_t kz = (int16_t)(round_s16(pos.z) >> kBlockLenBits);
-      pos.x += st.x;
-      pos.y += st.y;
-      pos.z += st.z;
-      key = pack_key(kx, ky, kz);
-    }
-    const int lane = lane_id();
-    const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
-    const uint32_t llo = __shfl_up(lo, 1, 64), lhi = __shfl_up(hi, 1, 64);
-    const uint32_t ulo = __shfl_up(lo, 16, 64), uhi = __shfl_up(hi, 16, 64);
-    const unsigned long long left = (lane & 15) ? (((unsigned long long)lhi << 32) | llo) : 0ull;
-    const unsigned long long up = lane >= 16 ? (((unsigned long long)uhi << 32) | ulo) : 0ull;
-    if (on && key != left && key != up && key != prev_key) {
-      const uint32_t order = order0 + (uint32_t)s;
-      uint32_t hs = tile_slot<TS>(key);
-      for (int p = 0; p < TS; ++p) {
-        const unsigned long long prev = atomicCAS(&s_key[hs], 0ull, key);
-        if (prev == 0ull || prev == key) {
-          atomicMin(&s_ord[hs], order);
-          break;
+  // lower: the wave's 16x4 pixels of each half are in raster order; the right half's first column
+  // has the left half's last column, 15 lanes up, to its left, and every right pixel its own lane's
+  // left pixel), or of the previous step at this pixel, is left out -- that sample has a smaller
+  // candidate order, and by induction some sample with the key and an order no larger is inserted. That removes most same-key LDS
+  // atomics (the serialised bank conflicts of r2's profile: 1.3 conflict cycles per LDS instruction
+  // cycle). A sample is one CAS, and one min more only when it meets its own key.
+  const int lane = lane_id();
+  const uint32_t lord0 = (uint32_t)(ly * 32 + lx) * (uint32_t)P.maxs, lord1 = lord0 + 16u * (uint32_t)P.maxs;
+  unsigned long long pk0 = 0ull, pk1 = 0ull;
+  for (int s = 0; s < P.maxs; ++s) {  // (uniform loop; the shuffles need every lane)
+    const unsigned long long k0 = tile_ray_key(r0, s), k1 = tile_ray_key(r1, s);
+    const unsigned long long l0 = shfl_up64(k0, 1), u0 = shfl_up64(k0, 16);
+    const unsigned long long l1 = shfl_up64(k1, 1), u1 = shfl_up64(k1, 16);
+    const uint32_t e_lo = __shfl_down((uint32_t)k0, 15, 64), e_hi = __shfl_down((uint32_t)(k0 >> 32), 15, 64);
+    const unsigned long long left0 = (lane & 15) ? l0 : 0ull;
+    const unsigned long long left1 = (lane & 15) ? l1 : (((unsigned long long)e_hi << 32) | e_lo);
+    const unsigned long long up0 = lane >= 16 ? u0 : 0ull, up1 = lane >= 16 ? u1 : 0ull;
+    bool a0 = k0 != 0ull && k0 != left0 && k0 != up0 && k0 != pk0;
+    bool a1 = k1 != 0ull && k1 != left1 && k1 != up1 && k1 != pk1 && k1 != k0;
+    pk0 = k0;
+    pk1 = k1;
+    const unsigned long long w0 = (k0 << kSlotOrdBits) | (lord0 + (uint32_t)s);
+    const unsigned long long w1 = (k1 << kSlotOrdBits) | (lord1 + (uint32_t)s);
+    uint32_t h0 = tile_slot<PS>(k0), h1 = tile_slot<PS>(k1);
+    // both samples' probe sequences advance together (bounded: the set has more slots than samples)
+    for (int p = 0; p < PS && (a0 || a1); ++p) {
+      unsigned long long p0 = 0ull, p1 = 0ull;
+      if (a0) p0 = atomicCAS(&s_slot[h0], 0ull, w0);
+      if (a1) p1 = atomicCAS(&s_slot[h1], 0ull, w1);
+      if (a0) {
+        if (p0 == 0ull || (p0 >> kSlotOrdBits) == k0) {
+          if (p0 != 0ull) atomicMin(&s_slot[h0], w0);
+          a0 = false;
+        } else {
+          h0 = (h0 + 1) & (PS - 1);
         }
-        hs = (hs + 1) & (TS - 1);
+      }
+      if (a1) {
+        if (p1 == 0ull || (p1 >> kSlotOrdBits) == k1) {
+          if (p1 != 0ull) atomicMin(&s_slot[h1], w1);
+          a1 = false;
+        } else {
+          h1 = (h1 + 1) & (PS - 1);
+        }
       }
     }
-    prev_key = key;
   }
   TSDF_STAMP(D, 0, 3);
   __syncthreads();
   TSDF_STAMP(D, 0, 4);
-  // Each wave sweeps its 64-slot strips; the few occupied slots of a strip (ballot) are tested
-  // 8 at a time with 8 lanes per key, one block corner per lane (is_block_visible<true>), and the
-  // fully visible ones are listed in LDS. The table probes and new-key inserts then run one key
-  // per lane over that list, so the wave pays their memory latency once, not once per 8 keys.
-  uint16_t(*s_vis)[TS / 4] = S.u.tile.vis;
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  // Each wave takes the 64-slot strips wave, wave + 4, ... and first packs their few occupied words
+  // (ballot) into a dense list in place: its i-th word goes to lane i % 64 of its (i / 64)-th strip, a
+  // slot of the strip in registers or of an earlier one (i is below the number of slots read so far),
+  // and no other wave reads or writes this wave's strips. The list is then tested 8 words at a time
+  // with 8 lanes per key, one block corner per lane (is_block_visible<true>), and the fully visible
+  // ones are packed again the same way (a word moves to a slot already read). The table probes and
+  // new-key inserts then run one key per lane over that list, so the wave pays their memory latency
+  // once, not once per 8 keys.
+  const int wave = threadIdx.x >> 6;
   const int grp = lane >> 3, corner = lane & 7;
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  auto own = [wave](int i) { return (wave + 4 * (i >> 6)) * 64 + (i & 63); };  // the wave's i-th slot
+  int nocc = 0;
+  for (int strip = wave; strip < PS / 64; strip += 4) {
+    const unsigned long long sw = s_slot[strip * 64 + lane];
+    const unsigned long long occ = __ballot(sw != 0ull);
+    if (sw != 0ull) s_slot[own(nocc + __popcll(occ & lanes_below))] = sw;
+    nocc += __popcll(occ);
+  }
   int nv = 0;
-  for (int strip = wave; strip < TS / 64; strip += 4) {
-    const unsigned long long skey = s_key[strip * 64 + lane];
-    const unsigned long long occ = __ballot(skey != 0ull);
-    const int n = __popcll(occ);
-    for (int base = 0; base < n; base += 8) {
-      const int want = base + grp;  // rank of the occupied slot this 8-lane group handles
-      int src = 0;                  // lane holding that slot: binary search on prefix popcounts
-#pragma unroll
-      for (int step = 32; step > 0; step >>= 1)
-        if (src + step < 64 && __popcll(occ & ((1ull << (src + step)) - 1ull)) <= want) src += step;
-      const unsigned long long key = __shfl(skey, src, 64);
-      bool vis = false;
-      if (want < n) {
-        int16_t kx, ky, kz;
-        unpack_key(key, kx, ky, kz);
-        vis = voxel_visible(P, (int16_t)((int16_t)(kx << kBlockLenBits) + ((corner >> 0) & 1) * (kBlockLen - 1)),
-                            (int16_t)((int16_t)(ky << kBlockLenBits) + ((corner >> 1) & 1) * (kBlockLen - 1)),
-                            (int16_t)((int16_t)(kz << kBlockLenBits) + ((corner >> 2) & 1) * (kBlockLen - 1)));
-      }
-      const unsigned long long bal = __ballot(vis);
-      const bool lead = want < n && corner == 0 && ((bal >> (lane & ~7)) & 0xFFull) == 0xFFull;
-      const unsigned long long leads = __ballot(lead);
-      if (lead) s_vis[wave][nv + __popcll(leads & ((1ull << lane) - 1ull))] = (uint16_t)(strip * 64 + src);
-      nv += __popcll(leads);
+  for (int base = 0; base < nocc; base += 8) {
+    const int k = base + grp;
+    unsigned long long word = 0ull;
+    bool vis = false;
+    if (k < nocc) {
+      word = s_slot[own(k)];
+      int16_t kx, ky, kz;
+      unpack_key(word >> kSlotOrdBits, kx, ky, kz);
+      vis = voxel_visible(P, (int16_t)((int16_t)(kx << kBlockLenBits) + ((corner >> 0) & 1) * (kBlockLen - 1)),
+                          (int16_t)((int16_t)(ky << kBlockLenBits) + ((corner >> 1) & 1) * (kBlockLen - 1)),
+                          (int16_t)((int16_t)(kz << kBlockLenBits) + ((corner >> 2) & 1) * (kBlockLen - 1)));
     }
+    const unsigned long long bal = __ballot(vis);
+    const bool lead = corner == 0 && ((bal >> (lane & ~7)) & 0xFFull) == 0xFFull;
+    const unsigned long long leads = __ballot(lead);
+    if (lead) s_slot[own(nv + __popcll(leads & lanes_below))] = word;  // (every word of the round is read)
+    nv += __popcll(leads);
   }
   TSDF_STAMP(D, 0, 6);  // (diag) corner tests done
   if (Mode == kTileChained) wait_tag(flag, tag, &D.ctr->status);  // the previous frame's allocation is published
   TSDF_STAMP(D, 0, 7);  // (diag) the allocation flag seen
   for (int i = lane; i < nv; i += 64) {
-    const int slot = s_vis[wave][i];
-    const unsigned long long key = s_key[slot];
+    const unsigned long long word = s_slot[own(i)];
+    const unsigned long long key = word >> kSlotOrdBits;
+    // the candidate order (y * W + x) * maxs + s of the word's pair-local one
+    const uint32_t lord = (uint32_t)word & ((1u << kSlotOrdBits) - 1u);
+    const uint32_t pix = lord / (uint32_t)P.maxs;
+    const uint32_t order = ((uint32_t)(y0 + (int)(pix >> 5)) * (uint32_t)P.W + (uint32_t)(x0 + (int)(pix & 31u))) *
+                               (uint32_t)P.maxs + (lord - pix * (uint32_t)P.maxs);
     int16_t kx, ky, kz;
     unpack_key(key, kx, ky, kz);
     const int32_t e = find_entry_t<Mode == kTileChained && kChainCoherentLoads>(D.table, kx, ky, kz);
     if (e >= 0) {
-      if (Mode == kTileChained) atomicMin(&D.fo[e], ((unsigned long long)~fid << 32) | s_ord[slot]);
+      if (Mode == kTileChained) atomicMin(&D.fo[e], ((unsigned long long)~fid << 32) | order);
       continue;
     }
-    nk_insert(D, key, s_ord[slot]);
+    nk_insert(D, key, order);
   }
   TSDF_STAMP(D, 0, 5);
 }

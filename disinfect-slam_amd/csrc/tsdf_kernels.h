@@ -114,9 +114,12 @@ constexpr int kPipeAPub = kPipeIngEnd + 32;     // + 16 p: allocation published 
 constexpr int kPipeStats = 512;                 // + 1024 p + 16 i: payload (blocks << 40 | voxels) and,
 constexpr int kPipeStatLines = 64;              //   at +1, the latest end stamp of update counter i
 constexpr int kPipeWords = kPipeStats + 2 * kPipeStatLines * 16;
-constexpr int kFrameUpdWgsPer2Cu = 5;           // default k_frame update workgroups per two CUs (TSDF_FRAME_WG_PER_CU)
+constexpr int kFrameUpdWgsPer4Cu = 11;          // default k_frame update workgroups per four CUs (TSDF_FRAME_WG_PER_CU)
 constexpr int kPipeHead = 8;                    // workgroups before the update's (0: carving + allocation)
-constexpr int kPipeFreshWG = 64;                // workgroups that update the blocks allocated in the launch
+#ifndef TSDF_PIPE_FRESH_WG  // (an experiment build overrides it)
+#define TSDF_PIPE_FRESH_WG 64
+#endif
+constexpr int kPipeFreshWG = TSDF_PIPE_FRESH_WG;  // workgroups that update the blocks allocated in the launch
 constexpr int kPipeDefer = 32;                  // deferred (carve-pending) blocks one update workgroup holds
 constexpr int kPipeList = 64;                   // records one update workgroup collects before updating them
 // What one k_frame launch does. Frame ids f are engine-wide (1, 2, ...); frame b's update, frame
@@ -131,8 +134,7 @@ struct PipeArgs {
   uint32_t tag;         // this launch's flag value
   uint32_t range;       // candidate order space of frame b (W H maxs)
   int tiles_x, tiles;   // frame c's pixel tiles
-  int tile_wgs;         // the workgroups that run them (tiles_per_wg consecutive tiles each)
-  int tiles_per_wg;
+  int tile_wgs;         // the workgroups that run them (tile_pair_wgs)
   int nint;             // update workgroups (a multiple of 8)
   int order;            // grid order of the parts after the head (TSDF_FRAME_ORDER): 0 fresh, update,
                         //   tiles, sweep; 1 fresh, tiles, sweep, update; 2 fresh, sweep, update, tiles;
@@ -158,6 +160,11 @@ __device__ __host__ __forceinline__ EngineDev frame_view(const EngineDev& D, uin
   V.cand = D.cand + (size_t)(f & 1u) * (size_t)D.cand_cap;
   V.ncand = reinterpret_cast<int32_t*>(D.pipe + kPipeNCand + 16 * (f & 1u));
   return V;
+}
+// The workgroups that run `tiles` 16x16 pixel tiles, whole rows of tiles_x: one per pair of
+// horizontally adjacent tiles of a row (ingest_tile, tsdf_ingest.h; an odd row's last one has one tile)
+__device__ __host__ __forceinline__ int tile_pair_wgs(int tiles_x, int tiles) {
+  return tiles_x > 0 ? (tiles / tiles_x) * ((tiles_x + 1) / 2) : 0;
 }
 // the workgroups that update the blocks a launch's allocation creates (orders 0-2)
 __device__ __host__ __forceinline__ int pipe_fresh_wgs(const PipeArgs& A) {
@@ -213,7 +220,7 @@ constexpr int kArrIngest = 0, kArrIntegrate = kArrStride, kArrStart = 2 * kArrSt
               kArriveWords = 2 * kArrStride + 32;
 // per frame (2 launches; the resolvers run in the last workgroup of each)
 constexpr int kVisWorkgroups = kOccWords / 256;  // visibility-sweep workgroups of k_ingest_dda
-template <int TS>  // LDS key-set slots per tile (tsdf_alloc.hip): 1024 for maxs <= 3, else 2048
+template <int TS>  // LDS key-set slots per tile, 2 TS per tile pair (tsdf_ingest.h): 1024 for maxs <= 3, else 2048
 __global__ void k_ingest_dda(EngineDev D, FrameParams P, const float* depth, const uint8_t* rgb,
                              const float* ht, const float* lt, int tiles_x, int tiles);
 // standalone one-workgroup resolvers (sharded frames after an exchange; the hash-level test path).
