@@ -483,43 +483,12 @@ __device__ __forceinline__ float quot_const(float a, float b, float rb) {
   return a / b;
 }
 
-// 16-B pool-state accesses: plain cached loads and stores. TSDF_STREAM_STORES / _LOADS build
-// nontemporal forms for timing studies (measured slower on MI355X: 18.3 / 20.2 us against 17.8 us
-// for k_integrate at the bench workload).
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 pool_ld(const uint8_t* p) {
-#if !defined(TSDF_STREAM_LOADS)
-  return *reinterpret_cast<const float4*>(p);
-#else
-  const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#endif
-}
-__device__ __forceinline__ uint4 pool_ldu(const uint8_t* p) {
-#if !defined(TSDF_STREAM_LOADS)
-  return *reinterpret_cast<const uint4*>(p);
-#else
-  const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-#endif
-}
-__device__ __forceinline__ void pool_st(uint8_t* p, float4 v) {
-#if !defined(TSDF_STREAM_STORES)
-  *reinterpret_cast<float4*>(p) = v;
-#else
-  const v4f t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
-#endif
-}
-__device__ __forceinline__ void pool_stu(uint8_t* p, uint4 v) {
-#if !defined(TSDF_STREAM_STORES)
-  *reinterpret_cast<uint4*>(p) = v;
-#else
-  const v4u t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<v4u*>(p));
-#endif
-}
+// 16-B pool-state accesses: plain cached loads and stores (nontemporal stores / loads measured slower on
+// MI355X: 18.3 / 20.2 us against 17.8 us for k_integrate at the bench workload).
+__device__ __forceinline__ float4 pool_ld(const uint8_t* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ uint4 pool_ldu(const uint8_t* p) { return *reinterpret_cast<const uint4*>(p); }
+__device__ __forceinline__ void pool_st(uint8_t* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void pool_stu(uint8_t* p, uint4 v) { *reinterpret_cast<uint4*>(p) = v; }
 
 // voxel_hash.cu:31-35
 __device__ __host__ __forceinline__ uint32_t hash_block(int16_t x, int16_t y, int16_t z) {

@@ -24,16 +24,10 @@ void set_error(const char* what) { g_last_error = what; }
 // none. TSDF_ROCTX (roctx ranges) is read on first use by the tracing wrapper.
 //   TSDF_PIPELINE=0               unpipelined frames: two launches per frame (k_ingest_dda, k_integrate)
 //   TSDF_PIPE_MAX_PIXELS=n        largest frame (pixels) that is pipelined (default 2^20: C4, 1280x720, is within it)
-//   TSDF_FRAME_ORDER=0..4         k_frame grid order of its parts (PipeArgs.order; default 2)
-//   TSDF_FRAME_WG_PER_CU=n        k_frame update workgroups per CU (default kFrameUpdWgsPer4Cu / 4 = 2.75: 704)
-//   TSDF_FRAME_UPD_WGS=n          (A/B) k_frame update workgroups in total (overrides the per-CU count)
-//   TSDF_INTEGRATE_WG_PER_CU=n    cap on k_integrate's resident workgroups per CU
+//   TSDF_FRAME_ORDER=0..2         k_frame grid order of its parts (PipeArgs.order; default 2)
+//   TSDF_FRAME_UPD_WGS=n          (A/B) k_frame update workgroups in total (default kFrameUpdWgsPer4Cu / 4 = 2.75 per CU: 704)
 //   TSDF_CAND_CAP=n               (tests) smaller carve-candidate list, to exercise its overflow
 //   TSDF_MESH_GRID=n              (tests) fewer k_mesh workgroups, to exercise its grid stride
-//   TSDF_RENDER_OVERLAP=1         raycast on a second stream overlapping the next frame
-//   TSDF_GRAPH_MEMCPY_NODE=1      (A/B) graph frames upload their arguments with a memcpy node
-//   TSDF_FUSE_VIEW_GRID=0         (A/B) the C5 loop's view grid in its own launch (render graphs: own node), not in the update's
-//   TSDF_UPLOAD_STREAMS=n         (A/B) host frames: upload streams a frame's copies spread over (1-4, default 2)
 // ---------------------------------------------------------------------------------------------
 static EnvKnobs read_env_knobs() {
   EnvKnobs k;
@@ -41,22 +35,12 @@ static EnvKnobs read_env_knobs() {
     const char* v = std::getenv(n);
     return v ? std::atoll(v) : dflt;
   };
-  auto flag = [](const char* n, bool dflt) {
-    const char* v = std::getenv(n);
-    return v ? v[0] == '1' : dflt;
-  };
   if (const char* v = std::getenv("TSDF_PIPELINE")) k.pipeline = v[0] != '0';
   k.pipe_max_pixels = num("TSDF_PIPE_MAX_PIXELS", -1);
   k.frame_order = (int)std::max(-1ll, num("TSDF_FRAME_ORDER", -1));
-  k.frame_wg_per_cu = (int)num("TSDF_FRAME_WG_PER_CU", 0);
   k.frame_upd_wgs = (int)num("TSDF_FRAME_UPD_WGS", 0);
-  k.integrate_wg_per_cu = (int)num("TSDF_INTEGRATE_WG_PER_CU", 0);
   k.cand_cap = (int)num("TSDF_CAND_CAP", 0);
   k.mesh_grid = (int)num("TSDF_MESH_GRID", 0);
-  k.render_overlap = flag("TSDF_RENDER_OVERLAP", false);
-  k.graph_memcpy_node = flag("TSDF_GRAPH_MEMCPY_NODE", false);
-  k.upload_streams = (int)num("TSDF_UPLOAD_STREAMS", 2);
-  k.fuse_view_grid = flag("TSDF_FUSE_VIEW_GRID", true);
   return k;
 }
 
@@ -73,7 +57,6 @@ tsdf_engine::~tsdf_engine() {
   for (auto& ev : events)
     for (hipEvent_t x : ev) (void)hipEventDestroy(x);
   if (order_ev) (void)hipEventDestroy(order_ev);
-  if (rstream) (void)hipStreamDestroy(rstream);
   for (int j = 0; j < kUpStreams; ++j) {
     if (ustream[j]) (void)hipStreamDestroy(ustream[j]);
     for (int k = 0; k < 2; ++k)
@@ -81,8 +64,6 @@ tsdf_engine::~tsdf_engine() {
   }
   for (int k = 0; k < 2; ++k)
     if (up_free[k]) (void)hipEventDestroy(up_free[k]);
-  if (rs_ready) (void)hipEventDestroy(rs_ready);
-  if (rs_done) (void)hipEventDestroy(rs_done);
   if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -134,12 +115,11 @@ FrameParams make_params(const tsdf_engine* e, const tsdf_intrinsics* K, int W, i
   return P;
 }
 
-// the engine stream waits for a raycast still running on the render stream
+// launches what an earlier call left pending: a batched graph's frames, then the deferred raycasts
 // (keep_deferred: a deferred raycast stays pending -- tsdf_stream_wait orders the engine stream after
-// another stream's work, which the raycast may follow as well; wait_overlap false: launch the deferred
-// raycasts only, without joining a TSDF_RENDER_OVERLAP raycast on the render stream -- the next
-// frame's ingest writes nothing it reads; keep_graph: the graph frame that renders rdg itself calls)
-int join_render(tsdf_engine* e, bool keep_deferred, bool wait_overlap, bool keep_graph) {
+// another stream's work, which the raycast may follow as well; keep_graph: the graph frame that
+// renders rdg itself calls)
+int join_render(tsdf_engine* e, bool keep_deferred, bool keep_graph) {
   if (e->gbatch) {  // the frames of a batched graph not launched yet, before anything else
     int rc = graph_flush_batch(e->gbatch);
     if (rc) return rc;
@@ -158,9 +138,6 @@ int join_render(tsdf_engine* e, bool keep_deferred, bool wait_overlap, bool keep
                        r.normal);
     HIP_OK(hipGetLastError());
   }
-  if (!e->render_pending || !wait_overlap) return TSDF_OK;
-  e->render_pending = false;
-  HIP_OK(hipStreamWaitEvent(e->stream, e->rs_done, 0));
   return TSDF_OK;
 }
 
@@ -328,7 +305,6 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kIntegrateThreads, 0) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
       return fail(TSDF_ERR_HIP);
-    if (e->env.integrate_wg_per_cu > 0) per_cu = std::min(per_cu, e->env.integrate_wg_per_cu);
     D.integrate_grid = std::max(8, std::min(kIntegrateGrid, (per_cu * ncu) & ~7));
     int per_cu_pre = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pre, reinterpret_cast<const void*>(k_frame),
@@ -344,7 +320,6 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
     // ahead (19.6k vs 18.7-19.4k at 640). Round 5 (log-odds state, 7 waves): 640 23.9k, 768
     // 23.3-23.5k, 512 23.4-23.7k; earlier rounds: 4 per CU 22.0-22.5k, 5 21.0-21.3k, 7 18.5-18.7k
     int upd = kFrameUpdWgsPer4Cu * ncu / 4;
-    if (e->env.frame_wg_per_cu > 0) upd = e->env.frame_wg_per_cu * ncu;
     if (e->env.frame_upd_wgs > 0) upd = e->env.frame_upd_wgs;
     D.integrate_grid_pre = std::max(8, std::min({kIntegrateGrid, upd, per_cu_pre * ncu}) & ~7);
   }
@@ -352,7 +327,7 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
   ALLOC(D.pixC, 2 * e->max_pixels);
   e->pipeline = e->env.pipeline;
   if (e->env.pipe_max_pixels >= 0) e->pipe_max_pixels = e->env.pipe_max_pixels;
-  if (e->env.frame_order >= 0) e->frame_order = std::min(4, e->env.frame_order);
+  if (e->env.frame_order >= 0) e->frame_order = std::min(2, e->env.frame_order);
   ALLOC(D.visbits, kOccWords);
   ALLOC(D.wgcnt, kOccWords / 256);
   ALLOC(D.dbg, (size_t)kDiagKernels * kDiagMaxWg * kDiagStamps);
@@ -400,11 +375,6 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
     if (
         hipEventCreateWithFlags(&e->up_free[k], hipEventDisableTiming) != hipSuccess)
       return fail(TSDF_ERR_HIP);
-  if (hipStreamCreateWithFlags(&e->rstream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->rs_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->rs_done, hipEventDisableTiming) != hipSuccess)
-    return fail(TSDF_ERR_HIP);
-  e->render_overlap = e->env.render_overlap;
   if (!init_state(e)) {
     set_error("tsdf_create: initialisation failed");
     return fail(TSDF_ERR_HIP);
@@ -417,7 +387,6 @@ int tsdf_destroy(tsdf_engine* e) {
   if (!e) return TSDF_ERR_INVALID_ARG;
   (void)hipSetDevice(e->device);
   (void)join_render(e);  // (a deferred raycast's outputs are still written)
-  if (e->rstream) (void)hipStreamSynchronize(e->rstream);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   delete e;
   return TSDF_OK;

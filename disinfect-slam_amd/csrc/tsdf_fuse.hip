@@ -205,11 +205,6 @@ __device__ __forceinline__ void update_issue_pool(const EngineDev& D, const VisR
   float4& ts = S.ts;
   float4& pr = S.pr;
   uint4& cw = S.cw;
-#if defined(TSDF_EXP) && (TSDF_EXP & 2)  // experiment build: no pool state loads
-  bool fresh;
-  ts = make_float4(0.5f, 0.5f, 0.5f, 0.5f), pr = ts;
-  cw = make_uint4(0x05808080u, 0x05808080u, 0x05808080u, 0x05808080u);
-#else
   const bool fresh = r.pad != 0;
   if (fresh) {  // wave-uniform: a block created this frame loads nothing
     ts = make_float4(-1.f, -1.f, -1.f, -1.f);
@@ -223,10 +218,6 @@ __device__ __forceinline__ void update_issue_pool(const EngineDev& D, const VisR
     pr = pool_ld(blk + kProbOffset + off);
     cw = pool_ldu(blk + kRgbwOffset + off);
   }
-#endif
-#if defined(TSDF_EXP) && (TSDF_EXP & 2)
-  fresh = r.pad != 0;
-#endif
   S.fresh = fresh;
 }
 template <bool Raw>
@@ -275,9 +266,6 @@ __device__ __forceinline__ void update_issue_pix(const EngineDev& D, const Frame
     for (int e = 0; e < 2; ++e) {
       const int j = 2 * k + e;
       inb[j] = uu[e] >= 0 && uu[e] < P.W && vv[e] >= 0 && vv[e] < P.H;
-#if defined(TSDF_EXP) && (TSDF_EXP & 1)  // experiment build: no pixel gathers
-      if (inb[j]) px[j] = make_float4(pcz[e] + 0.01f, 1.0f, 0.0f, 0.0f), pc[j] = 0x00808080u;
-#else
       // unconditional gathers at a clamped index (pixel 0 when out of the image): no exec-
       // masked region around the loads, so all 8 stay in flight until pass 2
       const int img = inb[j] ? vv[e] * P.W + uu[e] : 0;
@@ -290,7 +278,6 @@ __device__ __forceinline__ void update_issue_pix(const EngineDev& D, const Frame
         px[j] = D.pixA[P.pix_off + img];
         pc[j] = D.pixC[P.pix_off + img];
       }
-#endif
     }
   }
 }
@@ -403,7 +390,6 @@ __device__ __forceinline__ void update_finish(const EngineDev& D, const FramePar
   // (logf / expf: the oracle's fixed algorithms, sem_logf / sem_expf; the quotients IEEE-exact). The
   // fast path runs on both voxels of a pair; a voxel whose operands leave its range -- p 0 or 1, ht or
   // lt 0, extreme quotients -- is recomputed with every special case (sem_update_exact).
-#if !(defined(TSDF_EXP) && (TSDF_EXP & 8))  // (experiment build: no semantic update, timing only)
   // both pairs' fast chains first, with no branch between them (the compiler interleaves the two
   // dependency chains: +0.3 % frames/s, the update span -1 us, same box), then the rare exact
   // recomputations
@@ -437,12 +423,7 @@ __device__ __forceinline__ void update_finish(const EngineDev& D, const FramePar
       setc(pr, j, pn);
     }
   }
-#endif
-#if defined(TSDF_EXP) && (TSDF_EXP & 4)  // experiment build: no pool state stores
-  if (upd_mask < 0) {
-#else
   if (upd_mask == 0xF || fresh) {
-#endif
     // all four voxels written (a fresh block's untouched voxels get AquireBlock's state)
     pool_st(blk + off, ts);
     pool_st(blk + kProbOffset + off, pr);
@@ -575,10 +556,7 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
           s_cand[k] = r;
         } else {  // buffer full (heavy carving): publish this one now
           const int kg = atomicAdd(D.ncand, 1);
-          const unsigned long long* rv = reinterpret_cast<const unsigned long long*>(&r);
-          unsigned long long* dst = reinterpret_cast<unsigned long long*>(&D.cand[kg]);
-          st_co(&dst[0], rv[0]);
-          st_co(&dst[1], rv[1]);
+          st_rec_co(&D.cand[kg], r);
           s_ovf = 1;
         }
       }
@@ -597,12 +575,7 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
     int k0 = 0;
     if (lane == 0) k0 = atomicAdd(D.ncand, nc);
     k0 = __shfl(k0, 0, 64);
-    if (lane < nc) {
-      const unsigned long long* rv = reinterpret_cast<const unsigned long long*>(&s_cand[lane]);
-      unsigned long long* dst = reinterpret_cast<unsigned long long*>(&D.cand[k0 + lane]);
-      st_co(&dst[0], rv[0]);
-      st_co(&dst[1], rv[1]);
-    }
+    if (lane < nc) st_rec_co(&D.cand[k0 + lane], s_cand[lane]);
   }
   TSDF_STAMP(D, 3, 1);
 #ifdef TSDF_DIAG_STAMPS
@@ -1111,19 +1084,10 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   int bst = 0;
   int nvis = 0, nband = 0, p = 0, p_hi = 0, pstep = 1;
   bool carved_known = false;
-  // order 3: the whole update after the allocation flag -- no update traffic beside the head's
-  // carving and allocation (their chains of dependent round trips stretch ~4x under it), the new
-  // blocks listed after the band lists, and no deferral (the head publishes the carving first)
-  const bool after_alloc = kind == 0 && A.order >= 3;
   if (kind == 0) {
-    if (after_alloc) {
-      wait_tag(D.pipe + kPipeAlloc + (blockIdx.x & 7) * 16, A.tag, &D.ctr->status);
-      carved_known = true;
-    }
     bst = band_starts_p(D.band + (size_t)(fb % 3u) * kBands * kBandStride, lane, &nvis);
     nband = nvis;
     if (A.fresh_ready) nvis += D.ctr->n_fresh;
-    else if (after_alloc) nvis += ld_co(&D.ctr->n_fresh);
     // group g = blockIdx % 8 (one XCD) takes the g-th contiguous eighth of the pairs in band order
     // (a compact image region: its pixel records stay in that XCD's L2). (Measured and not kept:
     // pairs taken from 8 per-XCD queues by atomics, two at a time -- the update span grew 28 -> 38 us.)
@@ -1142,7 +1106,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   const uint32_t* ct = D.ctag + (size_t)(fc & 1u) * D.nblocks;
   int my_upd = 0, my_vis = 0, ndef = 0;
   bool def_done = false;
-  const bool fresh_co = kind != 0 || (after_alloc && !A.fresh_ready);  // (written in this launch)
+  const bool fresh_co = kind != 0;  // (written in this launch)
   // the collection is wave 0's: one record per lane (its list record and candidate tag gathered
   // together, two dependent round trips per collection instead of two per record), compacted into
   // s_list by ballot; the deferred candidates' release tags likewise one per lane
@@ -1331,8 +1295,6 @@ __device__ __forceinline__ int frame_part(const EngineDev& D, const FrameParams&
     return 1;
   }
   w -= kPipeHead;
-  if (A.order == 4)  // every part after the head's carving and allocation
-    wait_tag(D.pipe + kPipeAlloc + (blockIdx.x & 7) * 16, A.tag, &D.ctr->status);
   const int nfr = pipe_fresh_wgs(A);
   if (w < nfr) {  // the blocks this launch's allocation creates (they wait for it: dispatched early)
     if (TSDF_PRIO_UPD) __builtin_amdgcn_s_setprio(TSDF_PRIO_UPD);
@@ -1345,9 +1307,8 @@ __device__ __forceinline__ int frame_part(const EngineDev& D, const FrameParams&
   // (order r runs the parts r, r + 1, r + 2 mod 3; scalar selects, no indexed arrays: those live in
   // scratch)
   int part = -1, o = w;
-  const int ord = A.order == 3 ? 1 : (A.order == 4 ? 0 : A.order);
   for (int k = 0; k < 3; ++k) {
-    const int q = (ord + k) % 3;
+    const int q = (A.order + k) % 3;
     const int nq = q == 0 ? nold : (q == 1 ? A.tile_wgs : ns);
     if (o < nq) {
       part = q;

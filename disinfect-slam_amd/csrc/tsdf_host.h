@@ -142,11 +142,7 @@ struct TraceRange {
 struct EnvKnobs {
   bool pipeline = true;
   int64_t pipe_max_pixels = -1;
-  int frame_order = -1, frame_wg_per_cu = 0, integrate_wg_per_cu = 0, cand_cap = 0, mesh_grid = 0;
-  int frame_upd_wgs = 0;
-  bool render_overlap = false, graph_memcpy_node = false;
-  int upload_streams = 2;
-  bool fuse_view_grid = true;
+  int frame_order = -1, frame_upd_wgs = 0, cand_cap = 0, mesh_grid = 0;
 };
 
 struct tsdf_graph;  // tsdf_host_graph.hip
@@ -156,15 +152,6 @@ struct tsdf_engine {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  // render stream: k_raycast runs here so that the next frame's ingest (which writes neither the
-  // pool nor the view grid) overlaps it; every other call first joins it (join_render)
-  hipStream_t rstream = nullptr;
-  hipEvent_t rs_ready = nullptr, rs_done = nullptr;
-  bool render_pending = false;
-  // measured (r3, C5 loop, same box, interleaved): 5.44k frames/s with the overlap against 5.81k
-  // without -- the two cross-stream event waits per frame and the ingest's workgroups beside the
-  // raycast's cost more than the overlap hides. Off by default; TSDF_RENDER_OVERLAP=1 enables it.
-  bool render_overlap = false;
   // a deferred raycast (tsdf_raycast_deferred): its view grid is built; the k_raycast launch waits
   // for the engine's next call -- fused with the next frame's ingest (k_render_ingest) when that call
   // is tsdf_integrate, alone otherwise (join_render)
@@ -198,7 +185,7 @@ struct tsdf_engine {
   DevBuf<uint8_t> s_rgb;
   DevBuf<float> s_depth, s_ht, s_lt;
   // upload streams: a frame's copies spread over them (several DMA engines share the host link)
-  static constexpr int kUpStreams = 4;
+  static constexpr int kUpStreams = 2;
   hipStream_t ustream[kUpStreams] = {};
   hipEvent_t up_done[2][kUpStreams] = {};  // slot k's copies on stream j complete (the engine stream waits)
   int up_nstreams = 0;                     // streams the pending upload used
@@ -291,7 +278,7 @@ struct tsdf_engine {
   bool p_sampled = false;  // kPipeU: the frame was sampled for profiling (its update, when flushed
                            //   as k_integrate, takes an event pair then)
   uint32_t pipe_tag = 0;  // one per k_frame launch: its flags' value
-  int frame_order = 2;    // PipeArgs.order (TSDF_FRAME_ORDER): sweep, update, tiles (measured best)
+  int frame_order = 2;    // PipeArgs.order (TSDF_FRAME_ORDER, 0..2): sweep, update, tiles (measured best)
   EnvKnobs env;           // the environment's A/B and test knobs, read once at tsdf_create
   // feed_rgbd_frame staging: raw full-size inputs (host frames) and the half-size outputs
   // (fe_mask.cap / fe_out_depth.cap pixels)
@@ -314,7 +301,7 @@ struct tsdf_engine {
 // tsdf_engine.hip
 FrameParams make_params(const tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const tsdf_pose* p,
                         float max_depth);
-int join_render(tsdf_engine* e, bool keep_deferred = false, bool wait_overlap = true, bool keep_graph = false);
+int join_render(tsdf_engine* e, bool keep_deferred = false, bool keep_graph = false);
 int read_counters(tsdf_engine* e);
 bool init_state(tsdf_engine* e, bool with_pool = true);
 inline bool sharded(const tsdf_engine* e) { return e->cfg.shard_count > 1; }
@@ -356,7 +343,7 @@ inline int track_stage(tsdf_engine* e, size_t bytes) { return e->tk_stage.ensure
   } while (0)
 
 // every entry point that reads or writes the volume (or orders against it) first enqueues a deferred
-// update (pipelined frames) and joins the render stream
+// update (pipelined frames) and launches a deferred raycast or batch (join_render)
 #define ENTER(e)                       \
   do {                                 \
     int _rc = join_render(e);          \

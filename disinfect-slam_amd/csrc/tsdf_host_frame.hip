@@ -72,15 +72,14 @@ static int frame_ingest(tsdf_engine* e, const EngineDev& Dv, const tsdf_frame* f
     if (int rc = upload_release(e)) return rc;
     const int k = e->up_next;
     e->up_next ^= 1;
-    // the copies round-robin over the upload streams (TSDF_UPLOAD_STREAMS, default 2): the copies run on several DMA
-    // engines at once; the engine stream waits for each
-    const int nu = std::max(1, std::min(e->env.upload_streams, (int)tsdf_engine::kUpStreams));
+    // the copies round-robin over the upload streams: they run on several DMA engines at once; the
+    // engine stream waits for each
     const void* src[4] = {rgb, depth, ht, lt};
     const size_t bytes[4] = {np * 3, np * 4, np * 4, np * 4};
     void* dst[4] = {e->s_rgb + (size_t)k * e->max_pixels * 3, e->s_depth + (size_t)k * e->max_pixels,
                     e->s_ht + (size_t)k * e->max_pixels, e->s_lt + (size_t)k * e->max_pixels};
     const int ncopy = ht ? 4 : 2;
-    e->up_nstreams = std::min(nu, ncopy);
+    e->up_nstreams = std::min((int)tsdf_engine::kUpStreams, ncopy);
     for (int j = 0; j < e->up_nstreams; ++j)
       if (e->up_used[k]) HIP_OK(hipStreamWaitEvent(e->ustream[j], e->up_free[k], 0));
     for (int c = 0; c < ncopy; ++c)
@@ -145,11 +144,7 @@ static int frame_ingest(tsdf_engine* e, const EngineDev& Dv, const tsdf_frame* f
     LAUNCH_OK("k_render_ingest");
     return TSDF_OK;
   }
-  {  // a deferred raycast this ingest cannot take up runs first; a TSDF_RENDER_OVERLAP raycast on the
-     // render stream keeps overlapping this ingest (it writes nothing the raycast reads; the update joins it)
-    int rc = join_render(e, false, false);
-    if (rc) return rc;
-  }
+  JOIN_RENDER(e);  // a deferred raycast this ingest cannot take up runs first
   if (e->maxs <= 3)
     hipLaunchKernelGGL(k_ingest_dda<1024>, dim3(kVisWorkgroups + tile_pair_wgs(tiles_x, tiles)), dim3(256), 0, s, Dv, *P, depth,
                        rgb, ht, lt, tiles_x, tiles);
@@ -168,7 +163,7 @@ static int frame_ingest(tsdf_engine* e, const EngineDev& Dv, const tsdf_frame* f
 static int frame_update(tsdf_engine* e, const EngineDev& Dv, FrameParams P, std::array<hipEvent_t, 5>* ev,
                  void* cands_out = nullptr, int cand_cap = 0) {
   hipStream_t s = e->stream;
-  JOIN_RENDER(e);  // the update writes the pool a raycast on the render stream may still read
+  JOIN_RENDER(e);  // the update writes the pool a deferred raycast still pending reads
   const bool all_ev = ev && e->prof_mode == TSDF_PROFILE_PHASES;
   if (all_ev) HIP_OK(hipEventRecord((*ev)[1], s));
   P.tail = cands_out ? kTailPack : kTailResolve;

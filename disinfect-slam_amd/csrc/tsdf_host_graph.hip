@@ -118,7 +118,7 @@ int graph_create(tsdf_engine* e, int width, int height, int render_width, int re
         hipLaunchKernelGGL(k_ingest_dda_g<1024>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
       else
         hipLaunchKernelGGL(k_ingest_dda_g<2048>, dim3(kVisWorkgroups + tile_wgs), dim3(256), 0, g->cap, e->D, A);
-      if (render_width && e->env.fuse_view_grid)  // the render camera's view grid built in the update launch
+      if (render_width)  // the render camera's view grid built in the update launch
         hipLaunchKernelGGL(k_integrate_vg_g, dim3(e->D.integrate_grid + kOccWords / 256), dim3(kIntegrateThreads), 0,
                            g->cap, e->D, A, e->D.integrate_grid);
       else
@@ -126,7 +126,7 @@ int graph_create(tsdf_engine* e, int width, int height, int render_width, int re
                            g->cap, e->D, FrameParams{}, A);
     }
     if (render_width) {
-      if (g->pipe || !e->env.fuse_view_grid)
+      if (g->pipe)
         hipLaunchKernelGGL(k_view_grid_g, dim3(kOccWords / 256), dim3(256), 0, g->cap, e->D, A);
       hipLaunchKernelGGL(k_view_pack_g, dim3(kViewPackGrid), dim3(256), 0, g->cap, A);
       const dim3 rgrid((render_width + 15) / 16, (render_height + 15) / 16);
@@ -134,14 +134,11 @@ int graph_create(tsdf_engine* e, int width, int height, int render_width, int re
     }
   };
   // the args upload of entries [a0, a0 + n): one wave reads the pinned slots over the fabric (a kernel
-  // node, no DMA engine in the graph), or a memcpy node (A/B)
+  // node, no DMA engine in the graph)
   auto upload_node = [&](int a0, int n) {
-    if (e->env.graph_memcpy_node)
-      (void)hipMemcpyAsync(g->d_args + a0, g->h_args + a0, sizeof(FrameArgs) * n, hipMemcpyHostToDevice, g->cap);
-    else
-      hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(n > 1 ? 256 : 64), 0, g->cap,
-                         reinterpret_cast<uint32_t*>(g->d_args + a0), reinterpret_cast<const uint32_t*>(g->h_args + a0),
-                         (int)(sizeof(FrameArgs) * n / 4));
+    hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(n > 1 ? 256 : 64), 0, g->cap,
+                       reinterpret_cast<uint32_t*>(g->d_args + a0), reinterpret_cast<const uint32_t*>(g->h_args + a0),
+                       (int)(sizeof(FrameArgs) * n / 4));
   };
   auto capture = [&](hipGraph_t* gr, hipGraphExec_t* ex, int a0, int n) -> hipError_t {
     hipError_t er = hipStreamBeginCapture(g->cap, hipStreamCaptureModeThreadLocal);
@@ -378,7 +375,7 @@ int tsdf_graph_frame(tsdf_graph* g, const tsdf_frame* f, const tsdf_intrinsics* 
       int rc = graph_flush_batch(e->gbatch);
       if (rc) return rc;
     }
-    int rc = join_render(e, false, true, prev != nullptr);  // (not the raycast this launch takes)
+    int rc = join_render(e, false, prev != nullptr);  // (not the raycast this launch takes)
     if (!rc && !g->pipe) rc = flush_pending(e);  // (pipelined: the pending frames continue in this launch)
     if (rc) return rc;
   }

@@ -192,7 +192,7 @@ int raycast_impl(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const t
   // update's launch builds the view grid too (k_integrate_vg), one launch and boundary fewer
   bool fused = false;
   if (deferred && mem_kind == TSDF_MEM_DEVICE && e->ps == tsdf_engine::kPipeU && !sharded(e) &&
-      e->p_P.pack_pixels && e->env.fuse_view_grid) {
+      e->p_P.pack_pixels) {
     JOIN_RENDER(e);  // (a deferred raycast still pending reads the previous grid)
     rc = view_grid_for(e, P, step, kViewGraphBitmapWords, &V);
     if (rc) return rc;
@@ -226,22 +226,9 @@ int raycast_impl(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const t
     return TSDF_OK;
   }
   const size_t lds = V.n ? (size_t)V.nw * 4 : 0;
-  // With a view grid the raycast reads only the pool, the grid and its bitmaps, none of which the
-  // next frame's ingest writes: it runs on the render stream, overlapping that ingest (the next
-  // update and every other call join it first). Without a grid it reads the hash table: engine stream.
-  const bool overlap = e->render_overlap && V.n;
-  hipStream_t rs = overlap ? e->rstream : e->stream;
-  if (overlap) {
-    HIP_OK(hipEventRecord(e->rs_ready, e->stream));
-    HIP_OK(hipStreamWaitEvent(rs, e->rs_ready, 0));
-  }
   const dim3 rgrid((W + 15) / 16, (nrows + 15) / 16);
-  hipLaunchKernelGGL(k_raycast, rgrid, dim3(256), lds, rs, e->D, P, step, V, o1, o2);
+  hipLaunchKernelGGL(k_raycast, rgrid, dim3(256), lds, e->stream, e->D, P, step, V, o1, o2);
   LAUNCH_OK("k_raycast");
-  if (overlap) {
-    HIP_OK(hipEventRecord(e->rs_done, rs));
-    e->render_pending = true;
-  }
   if (mem_kind == TSDF_MEM_HOST) {
     ENTER(e);
     const size_t bytes = (size_t)W * nrows * 4;

@@ -447,11 +447,6 @@ __device__ __forceinline__ void vis_sweep_chained(const EngineDev& D, const Fram
 // tagged ~fid, and the carving re-inserts the keys it deletes (tsdf_resolve.h carved_key). Missing keys
 // stay missing (a carving only deletes), so they go to the new-key set now.
 constexpr int kTileFull = 0, kTileChained = 1;
-#ifdef TSDF_CHAIN_PLAIN
-constexpr bool kChainCoherentLoads = false;
-#else
-constexpr bool kChainCoherentLoads = true;
-#endif
 
 // A slot of the pair's key set is one word: the block key (pack_key: 49 bits) above the sample's
 // pair-local candidate order ((ly * 32 + lx) * maxs + s < 512 * 6), 0 when empty. The local order is
@@ -680,7 +675,7 @@ __device__ __forceinline__ void ingest_tile(const EngineDev& D, const FrameParam
                                (uint32_t)P.maxs + (lord - pix * (uint32_t)P.maxs);
     int16_t kx, ky, kz;
     unpack_key(key, kx, ky, kz);
-    const int32_t e = find_entry_t<Mode == kTileChained && kChainCoherentLoads>(D.table, kx, ky, kz);
+    const int32_t e = find_entry_t<Mode == kTileChained>(D.table, kx, ky, kz);
     if (e >= 0) {
       if (Mode == kTileChained) atomicMin(&D.fo[e], ((unsigned long long)~fid << 32) | order);
       continue;

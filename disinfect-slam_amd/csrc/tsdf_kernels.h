@@ -114,7 +114,7 @@ constexpr int kPipeAPub = kPipeIngEnd + 32;     // + 16 p: allocation published 
 constexpr int kPipeStats = 512;                 // + 1024 p + 16 i: payload (blocks << 40 | voxels) and,
 constexpr int kPipeStatLines = 64;              //   at +1, the latest end stamp of update counter i
 constexpr int kPipeWords = kPipeStats + 2 * kPipeStatLines * 16;
-constexpr int kFrameUpdWgsPer4Cu = 11;          // default k_frame update workgroups per four CUs (TSDF_FRAME_WG_PER_CU)
+constexpr int kFrameUpdWgsPer4Cu = 11;          // default k_frame update workgroups per four CUs (TSDF_FRAME_UPD_WGS)
 constexpr int kPipeHead = 8;                    // workgroups before the update's (0: carving + allocation)
 #ifndef TSDF_PIPE_FRESH_WG  // (an experiment build overrides it)
 #define TSDF_PIPE_FRESH_WG 64
@@ -137,10 +137,7 @@ struct PipeArgs {
   int tile_wgs;         // the workgroups that run them (tile_pair_wgs)
   int nint;             // update workgroups (a multiple of 8)
   int order;            // grid order of the parts after the head (TSDF_FRAME_ORDER): 0 fresh, update,
-                        //   tiles, sweep; 1 fresh, tiles, sweep, update; 2 fresh, sweep, update, tiles;
-                        //   3 tiles, sweep, update, the update after the allocation flag (no fresh
-                        //   workgroups: the update takes the new blocks too); 4 update, tiles, sweep,
-                        //   every part after the allocation flag (the head's resolvers alone)
+                        //   tiles, sweep; 1 fresh, tiles, sweep, update; 2 fresh, sweep, update, tiles
   // a shard's pipelined frame (tsdf_integrate_shard_pipe): every shard's carve candidates of frame
   // fid_carve, all-gathered (nshard slots of cand_cap records; merged before the carving), and this
   // shard's slot that the update's last workgroup fills with frame fid_alloc's candidates
@@ -166,9 +163,9 @@ __device__ __host__ __forceinline__ EngineDev frame_view(const EngineDev& D, uin
 __device__ __host__ __forceinline__ int tile_pair_wgs(int tiles_x, int tiles) {
   return tiles_x > 0 ? (tiles / tiles_x) * ((tiles_x + 1) / 2) : 0;
 }
-// the workgroups that update the blocks a launch's allocation creates (orders 0-2)
+// the workgroups that update the blocks a launch's allocation creates
 __device__ __host__ __forceinline__ int pipe_fresh_wgs(const PipeArgs& A) {
-  return A.has_update && !A.fresh_ready && A.order < 3 ? kPipeFreshWG : 0;
+  return A.has_update && !A.fresh_ready ? kPipeFreshWG : 0;
 }
 // per-frame arguments of the graph-captured frame loop (tsdf_graph_*): the graph's first node
 // copies them from a pinned host slot, every graph kernel reads its camera / frame pointers here

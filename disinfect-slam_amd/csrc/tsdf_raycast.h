@@ -343,11 +343,7 @@ __device__ __forceinline__ void raycast(const EngineDev& D, const FrameParams& P
     else if (valid)
       surface_store(S, idx, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f, 0u);
   } else if (hit) {
-#if defined(TSDF_EXP) && (TSDF_EXP & 8)  // experiment build: no shading (timing of the march alone)
-    if (rgba) rgba[idx] = make_uchar4(255, 255, 255, 255);
-#else
     ray_shade(D, R, c, hit_pos, sg, dw, rgba, normal, idx);
-#endif
   } else if (valid) {
     if (rgba) rgba[idx] = make_uchar4(0, 0, 0, 0);
     if (normal) normal[idx] = make_uchar4(0, 0, 0, 0);

@@ -97,9 +97,6 @@ def main():
                     dur = (s[:, b] - s[:, a]) * 10e-3
                     d.setdefault(p, []).append(np.median(dur))
                     d.setdefault(p + "_max", []).append(dur.max())
-        if S[1, 0, 7] > 0:  # TSDF_EXP & 16 diag build: the resolver's sort repeated (warm)
-            acc.setdefault("resolve_alloc sort repeated", {}).setdefault("sort2", []).append(
-                (S[1, 0, 7] - S[1, 0, 2]) * 10e-3)
         # k_integrate placement (diag build): per CU (xcc, se, cu) the pairs of its workgroups and
         # the latest end; per pair count the workgroups' end times
         s3 = S[3]

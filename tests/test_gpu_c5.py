@@ -248,8 +248,8 @@ def test_c5_deferred_graph_equals_graph():
 def test_deferred_raycast_heavy_carving():
     """The C5 loop's view grid built inside the update launch (k_integrate_vg) before that launch's
     carving, which then clears the cells of the blocks it released: 2 cm voxels at 96x72 carve many
-    blocks per frame; the deferred images equal the immediate raycast's frame by frame (also with
-    TSDF_FUSE_VIEW_GRID's separate launch as the reference, the immediate path)."""
+    blocks per frame; the deferred images equal the immediate raycast's frame by frame (the immediate
+    path, the reference here, builds its grid in a launch of its own, k_view_grid)."""
     import torch
 
     import tsdf_amd

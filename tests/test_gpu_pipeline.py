@@ -74,6 +74,54 @@ def test_pipelined_stream_equals_oracle_heavy_carving():
         ora.close()
 
 
+@pytest.fixture(scope="module")
+def heavy_oracles():
+    """The oracle after 8 and after 16 frames of the heavy-carving stream (computed once, only read)."""
+    from tsdf_amd import synth
+    from _oracle import OracleGrid
+    cam = synth.camera(96, 72)
+    oras = {n: OracleGrid(0.02, 0.08, 13) for n in (8, 16)}
+    for f in range(16):
+        fr = synth.render(cam, f)
+        for n, ora in oras.items():
+            if f < n:
+                ora.integrate(fr["rgb"], fr["depth"], fr["ht"], fr["lt"], 4.0, cam.K, fr["q"], fr["t"])
+    yield oras
+    for ora in oras.values():
+        ora.close()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_pipelined_stream_frame_orders(order, heavy_oracles):
+    """The other two grid orders of k_frame's parts (TSDF_FRAME_ORDER 0 and 1; 2 is the default every
+    other test runs) on the heavy-carving stream: allocation, carving, deferred candidates and fresh
+    blocks in every launch, the oracle compared at frames 8 and 16."""
+    import tsdf_amd
+    from tsdf_amd import synth
+    cam = synth.camera(96, 72)
+    old = os.environ.get("TSDF_FRAME_ORDER")
+    os.environ["TSDF_FRAME_ORDER"] = str(order)
+    try:
+        eng = _engine(True, 0.02, 0.08, max_width=96, max_height=72, num_block_bits=13)
+    finally:
+        if old is None:
+            del os.environ["TSDF_FRAME_ORDER"]
+        else:
+            os.environ["TSDF_FRAME_ORDER"] = old
+    try:
+        eng.profile_begin()
+        for f in range(16):
+            fr = synth.render(cam, f)
+            eng.integrate(fr["rgb"], fr["depth"], fr["ht"], fr["lt"], cam.K, tsdf_amd.SE3(fr["q"], fr["t"]), 4.0)
+            if f + 1 in heavy_oracles:
+                compare(eng, heavy_oracles[f + 1], tag=f"order {order}, frame {f}")
+                assert eng.stats()["status"] == 0
+        prof = eng.profile_end()
+        assert prof["pipelined"] >= 13, prof  # every frame but the two after a dump and the first
+    finally:
+        eng.close()
+
+
 def test_pipelined_equals_unpipelined_bench_stream():
     """The bench's 640x480 stream, 60 frames back to back into a pipelined and an unpipelined engine:
     the whole state bit for bit."""
