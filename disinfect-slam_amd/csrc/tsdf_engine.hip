@@ -54,6 +54,8 @@ tsdf_engine::~tsdf_engine() {
   if (h_ctr) (void)hipHostFree(h_ctr);
   if (uv_h) (void)hipHostFree(uv_h);
   if (uv_ev) (void)hipEventDestroy(uv_ev);
+  if (pl_h) (void)hipHostFree(pl_h);
+  if (pl_ev) (void)hipEventDestroy(pl_ev);
   for (auto& ev : events)
     for (hipEvent_t x : ev) (void)hipEventDestroy(x);
   if (order_ev) (void)hipEventDestroy(order_ev);

@@ -237,6 +237,18 @@ struct tsdf_engine {
   int32_t uv_cap = 0;  // emitters
   hipEvent_t uv_ev = nullptr;
   bool uv_busy = false;
+  // lamp-stop planning (tsdf_uv_irradiance / tsdf_uv_plan; tsdf_host_plan.hip), grow-only. pl_dev: an
+  // irradiance call's emitters, candidate offsets, 8 box words and one flag per emitter, or a plan's
+  // PlanState, gains and stops; pl_h (pl_cap bytes) the pinned copy they are uploaded from / read back to,
+  // free again once pl_ev has passed. pl_part: k_plan_gain's sums. pl_stage: a plan's host arrays staged
+  // on the device.
+  DevBuf<uint8_t> pl_dev;
+  uint8_t* pl_h = nullptr;
+  size_t pl_cap = 0;
+  hipEvent_t pl_ev = nullptr;
+  bool pl_busy = false;
+  DevBuf<double> pl_part;
+  DevBuf<uint8_t> pl_stage;
   // hash-level test scratch (tsdf_hash_* / tsdf_pool_*): t_s4.cap points
   DevBuf<int16_t> t_keys;
   DevBuf<VisRec> t_recs;
@@ -331,6 +343,11 @@ void view_shape_half(const tsdf_engine* e, int half, int lds_words, ViewShape* o
 bool view_grid_resets(const tsdf_engine* e, const FrameParams& P, float step_size, int lds_words);
 int view_grid_take(tsdf_engine* e, const ViewShape& S, ViewGrid* V);
 int view_grid_for(tsdf_engine* e, const FrameParams& P, float step_size, int lds_words, ViewGrid* V);
+// tsdf_host_dose.hip: the block grid of a dose launch with A's receivers and emitters (em: their host
+// copy). box: 8 + A.m device words (6 box words, two spare, one flag per emitter), hbox the same in pinned
+// memory. Synchronises the stream once. *V keeps n == 0 (hash lookups) when the rays' cube is wider than a grid.
+int dose_view_grid(tsdf_engine* e, DoseParams& A, const tsdf_uv_emitter* em, int32_t* box, int32_t* hbox,
+                   ViewGrid* V);
 // tsdf_host_track.hip: tracking, surface maps and dose are refused on a shard engine
 bool track_refused(const tsdf_engine* e, const char* what);
 // room for `bytes` of host maps / frames staged on the device

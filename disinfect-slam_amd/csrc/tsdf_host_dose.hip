@@ -42,13 +42,76 @@ int dose_buffers(tsdf_engine* e, int32_t m) {
   return TSDF_OK;
 }
 
+}  // namespace
+
+// (tsdf_host.h; tsdf_uv_irradiance shares it) The block grid of a dose launch: a cube over the ray origins of the irradiated receivers
+// and the emitters that irradiate one (k_dose_bounds), two voxels of room around them. Every sample lies
+// between a ray's two ends, so inside the box; a lookup outside the grid would go to the hash table all
+// the same.
+int dose_view_grid(tsdf_engine* e, DoseParams& A, const tsdf_uv_emitter* em, int32_t* box, int32_t* hbox,
+                   ViewGrid* Vp) {
+  ViewGrid& V = *Vp;
+  hipStream_t s = e->stream;
+  const int32_t m = A.m;
+  const dim3 grid((unsigned)((A.n + 255) / 256));
+  int32_t* flag = box + 8;
+  for (int a = 0; a < 3; ++a) hbox[a] = INT32_MAX, hbox[3 + a] = INT32_MIN;
+  std::memset(hbox + 8, 0, (size_t)m * 4);
+  HIP_OK(hipMemcpyAsync(box, hbox, 32 + (size_t)m * 4, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_dose_bounds, grid, dim3(256), 0, s, A, box, flag);
+  LAUNCH_OK("k_dose_bounds");
+  HIP_OK(hipMemcpyAsync(hbox, box, 32 + (size_t)m * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  const int32_t* hflag = hbox + 8;
+  double lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) lo[a] = hbox[a], hi[a] = hbox[3 + a];
+  for (int32_t k = 0; k < m; ++k) {
+    if (!hflag[k]) continue;
+    const float ec[3] = {em[k].x, em[k].y, em[k].z};
+    for (int a = 0; a < 3; ++a) {
+      const double v = (double)(ec[a] / A.voxel - A.offset);
+      lo[a] = std::min(lo[a], std::floor(v));
+      hi[a] = std::max(hi[a], std::ceil(v));
+    }
+  }
+  bool ok = lo[0] <= hi[0];  // (some receiver is irradiated)
+  int cb[3] = {0, 0, 0}, half = 0;
+  for (int a = 0; ok && a < 3; ++a) {
+    ok = lo[a] > -1e6 && hi[a] < 1e6;
+    if (!ok) break;
+    const int b0 = ((int)lo[a] - 2) >> kBlockLenBits, b1 = ((int)hi[a] + 2) >> kBlockLenBits;
+    cb[a] = (b0 + b1) >> 1;
+    half = std::max(half, std::max(cb[a] - b0, b1 - cb[a]));
+  }
+  if (ok && 2 * half + 1 <= kViewMaxN) {  // (a wider box: hash lookups, V.n stays 0)
+    ViewShape S;
+    view_shape_half(e, half, kViewBitmapWords, &S);
+    if (int rc = view_grid_take(e, S, &V)) return rc;
+  }
+  if (V.n) {
+    // k_view_grid places the cube by a camera centre: the centre block's first voxel, in voxel units
+    FrameParams P{};
+    P.voxel = 1.0f;
+    P.wt = {(float)(cb[0] * kBlockLen), (float)(cb[1] * kBlockLen), (float)(cb[2] * kBlockLen)};
+    A.ox = cb[0] - half;
+    A.oy = cb[1] - half;
+    A.oz = cb[2] - half;
+    hipLaunchKernelGGL(k_view_grid, dim3(kOccWords / 256), dim3(256), 0, s, e->D, P, V);
+    hipLaunchKernelGGL(k_view_pack, dim3(kViewPackGrid), dim3(256), 0, s, V);
+    LAUNCH_OK("k_view_grid");
+  }
+  return TSDF_OK;
+}
+
+namespace {
+
 // tsdf_uv_dose on device arrays (after ENTER)
 int dose_launch(tsdf_engine* e, const float* points, const float* normals, int64_t n, const tsdf_uv_emitter* em,
                 int32_t m, const tsdf_uv_config& c, float* dose) {
   int rc = dose_buffers(e, m);
   if (rc) return rc;
   hipStream_t s = e->stream;
-  const size_t o_box = (size_t)e->uv_cap * 16, o_flag = o_box + 32;
+  const size_t o_box = (size_t)e->uv_cap * 16;  // (then the flags, 32 bytes on)
   std::memcpy(e->uv_h, em, (size_t)m * 16);
   HIP_OK(hipMemcpyAsync(e->uv_dev, e->uv_h, (size_t)m * 16, hipMemcpyHostToDevice, s));
   DoseParams A{};
@@ -70,58 +133,9 @@ int dose_launch(tsdf_engine* e, const float* points, const float* normals, int64
   V.flags = e->vg_flags;
   V.bits = e->vg_bits;
   if (c.use_grid) {
-    // The block grid: a cube over the ray origins of the irradiated receivers and the emitters that
-    // irradiate one (k_dose_bounds), two voxels of room around them. Every sample lies between a ray's
-    // two ends, so inside the box; a lookup outside the grid would go to the hash table all the same.
-    int32_t* box = reinterpret_cast<int32_t*>(e->uv_dev + o_box);
-    int32_t* flag = reinterpret_cast<int32_t*>(e->uv_dev + o_flag);
-    int32_t* hbox = reinterpret_cast<int32_t*>(e->uv_h + o_box);
-    for (int a = 0; a < 3; ++a) hbox[a] = INT32_MAX, hbox[3 + a] = INT32_MIN;
-    std::memset(e->uv_h + o_flag, 0, (size_t)m * 4);
-    HIP_OK(hipMemcpyAsync(box, hbox, 32 + (size_t)m * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_dose_bounds, grid, dim3(256), 0, s, A, box, flag);
-    LAUNCH_OK("k_dose_bounds");
-    HIP_OK(hipMemcpyAsync(hbox, box, 32 + (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    const int32_t* hflag = reinterpret_cast<const int32_t*>(e->uv_h + o_flag);
-    double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) lo[a] = hbox[a], hi[a] = hbox[3 + a];
-    for (int32_t k = 0; k < m; ++k) {
-      if (!hflag[k]) continue;
-      const float ec[3] = {em[k].x, em[k].y, em[k].z};
-      for (int a = 0; a < 3; ++a) {
-        const double v = (double)(ec[a] / A.voxel - A.offset);
-        lo[a] = std::min(lo[a], std::floor(v));
-        hi[a] = std::max(hi[a], std::ceil(v));
-      }
-    }
-    bool ok = lo[0] <= hi[0];  // (some receiver is irradiated)
-    int cb[3] = {0, 0, 0}, half = 0;
-    for (int a = 0; ok && a < 3; ++a) {
-      ok = lo[a] > -1e6 && hi[a] < 1e6;
-      if (!ok) break;
-      const int b0 = ((int)lo[a] - 2) >> kBlockLenBits, b1 = ((int)hi[a] + 2) >> kBlockLenBits;
-      cb[a] = (b0 + b1) >> 1;
-      half = std::max(half, std::max(cb[a] - b0, b1 - cb[a]));
-    }
-    if (ok && 2 * half + 1 <= kViewMaxN) {  // (a wider box: hash lookups, V.n stays 0)
-      ViewShape S;
-      view_shape_half(e, half, kViewBitmapWords, &S);
-      rc = view_grid_take(e, S, &V);
-      if (rc) return rc;
-    }
-    if (V.n) {
-      // k_view_grid places the cube by a camera centre: the centre block's first voxel, in voxel units
-      FrameParams P{};
-      P.voxel = 1.0f;
-      P.wt = {(float)(cb[0] * kBlockLen), (float)(cb[1] * kBlockLen), (float)(cb[2] * kBlockLen)};
-      A.ox = cb[0] - half;
-      A.oy = cb[1] - half;
-      A.oz = cb[2] - half;
-      hipLaunchKernelGGL(k_view_grid, dim3(kOccWords / 256), dim3(256), 0, s, e->D, P, V);
-      hipLaunchKernelGGL(k_view_pack, dim3(kViewPackGrid), dim3(256), 0, s, V);
-      LAUNCH_OK("k_view_grid");
-    }
+    rc = dose_view_grid(e, A, em, reinterpret_cast<int32_t*>(e->uv_dev + o_box),
+                        reinterpret_cast<int32_t*>(e->uv_h + o_box), &V);
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(k_uv_dose, grid, dim3(256), V.n ? (size_t)V.nw * 4 : 0, s, e->D, A, V);
   LAUNCH_OK("k_uv_dose");

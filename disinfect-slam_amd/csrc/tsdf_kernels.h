@@ -355,6 +355,41 @@ __global__ void k_uv_dose(EngineDev D, DoseParams A, ViewGrid V);
 // coordinate of the ray origins of receivers some emitter irradiates (integer min / max: any order gives
 // the same box), eflag[k] = 1 for an emitter in range of a receiver. box starts at {INT_MAX x 3, INT_MIN x 3}.
 __global__ void k_dose_bounds(DoseParams A, int32_t* box, int32_t* eflag);
+// Lamp-stop planning (tsdf_plan.hip; DESIGN.md "Lamp-stop planning")
+// k_uv_dose with the candidate as the grid's second dimension: workgroup row y marches candidate
+// c = c0 + y's emitters first[c] .. first[c + 1] - 1 of A.emit in order and writes out[c * A.n + i] for every
+// receiver (0 without a normal); A.dose is not used (dynamic LDS: V.nw words)
+__global__ void k_uv_irradiance(EngineDev D, DoseParams A, ViewGrid V, const int32_t* first, int c0, float* out);
+// the greedy plan on a C x n matrix E: what a round leaves for the next launch and for the host
+struct PlanState {
+  int32_t stopped;  // a round found no candidate worth a stop: every later launch returns at once
+  int32_t nstops;   // rounds that chose a stop
+  int32_t best;     // the last chosen candidate (k_plan_apply's row)
+  int32_t pad;
+};
+struct PlanArgs {
+  const float* E;
+  float* need;
+  const float* weight;  // null: all 1
+  int64_t n;
+  int C;
+  double* part;         // [chunk][candidate]: k_plan_gain's per-workgroup sums
+  PlanState* state;
+  double* gains;        // one per round
+  int32_t* stops;
+};
+// receivers per k_plan_gain workgroup: kPlanItems per thread, 256 apart (coalesced)
+constexpr int kPlanItems = 16, kPlanChunk = 256 * kPlanItems;
+// candidates per k_plan_gain workgroup: they share the chunk's need and weight
+constexpr int kPlanRows = 4;
+// grid (chunks, groups of kPlanRows candidates from c0): part[chunk * C + c] = the chunk's share of
+// candidate c's gain
+__global__ void k_plan_gain(PlanArgs P, int c0);
+// one workgroup: the G chunks of every candidate added in index order, the best candidate (lowest index
+// between equal gains), and round r's decision: stop, or stops[r] / gains[r] / state->best
+__global__ void k_plan_final(PlanArgs P, int G, int r, float min_gain);
+// need[i] = fmaxf(need[i] - E[best][i], 0) where E[best][i] > 0; one thread per receiver
+__global__ void k_plan_apply(PlanArgs P);
 // Euclidean distance field over a box (tsdf_edt.hip; DESIGN.md "Distance field"). The box, its cover by
 // whole blocks, and the site bitmap's shape: one row of rowbytes bytes (a multiple of 4, the padding zero)
 // per (z, y) of the box, byte b of a row the eight voxels of the cover's b-th block along x.

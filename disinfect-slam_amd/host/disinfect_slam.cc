@@ -78,4 +78,26 @@ void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitte
   TSDF_->AccumulateDose(mesh.verts, mesh.normals, emitters, &mesh.dose, &c);
 }
 
+DISINFSystem::LampPlan DISINFSystem::plan_irradiation(TriMesh& mesh, const std::vector<float>& dose, float target,
+                                                      const LampCandidates& candidates, int max_stops, float min_gain,
+                                                      float prob_min, const tsdf_uv_config* cfg) {
+  const size_t nv = mesh.verts.size() / 3;
+  if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);
+  if (mesh.normals.size() != mesh.verts.size() || mesh.prob.size() != nv || (!dose.empty() && dose.size() != nv))
+    throw std::invalid_argument("DISINFSystem::plan_irradiation: normals / prob / dose do not match the vertices");
+  tsdf_uv_config c;
+  if (cfg)
+    c = *cfg;
+  else
+    tsdf_uv_config_default(TSDF_->engine(), &c);
+  c.sample_offset = 0.5f;
+  const std::vector<float> E = TSDF_->Irradiance(mesh.verts, mesh.normals, candidates.emitters, candidates.first, &c);
+  LampPlan plan;
+  plan.need = plan_need(dose.empty() ? std::vector<float>(nv, 0.0f) : dose, mesh.prob, target, prob_min);
+  std::vector<float> weight = vertex_area(mesh.verts, mesh.tris);
+  for (size_t i = 0; i < nv; ++i) weight[i] = weight[i] * mesh.prob[i];
+  plan.stops = TSDF_->PlanStops(E, candidates.size(), &plan.need, weight, max_stops, min_gain, &plan.gains);
+  return plan;
+}
+
 }  // namespace disinfect

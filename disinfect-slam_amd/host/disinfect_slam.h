@@ -44,6 +44,20 @@ class DISINFSystem {
   // accumulates into mesh.dose, sized and zeroed when empty. carry_dose (uv_dose.h) moves the dose of an
   // earlier extraction over by mesh.keys.
   void irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg = nullptr);
+  // Where to hold the lamp next (DESIGN.md "Lamp-stop planning"): the greedy choice of at most max_stops
+  // of the candidates (tube_candidates of standoff_candidates, uv_dose.h) against what the high-touch
+  // surface of a query_mesh result still lacks -- need = plan_need(dose, mesh.prob, target, prob_min), dose
+  // one value per vertex (empty: zeros), weight = vertex_area * mesh.prob. Fills mesh.normals when empty,
+  // as irradiate does. stops[r] is the candidate of round r, gains[r] the weighted dose it removed, need
+  // what is still missing after the stops. The same inputs give the same plan.
+  struct LampPlan {
+    std::vector<int32_t> stops;
+    std::vector<double> gains;
+    std::vector<float> need;
+  };
+  LampPlan plan_irradiation(TriMesh& mesh, const std::vector<float>& dose, float target,
+                            const LampCandidates& candidates, int max_stops = 16, float min_gain = 0.0f,
+                            float prob_min = 0.5f, const tsdf_uv_config* cfg = nullptr);
   // The clearance layer a lamp planner asks: squared Euclidean distances [voxels^2] from every voxel whose
   // centre lies in `volumn` to the nearest surface voxel there, saturated at max_dist^2, with the voxels'
   // state (TSDFGrid::DistanceField). unknown: never-observed space is an obstacle as well.

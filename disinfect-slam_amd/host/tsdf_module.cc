@@ -112,6 +112,24 @@ void TSDFSystem::AccumulateDose(const std::vector<float>& points, const std::vec
   tsdf_.AccumulateDose(points, normals, emitters, dose, cfg);
 }
 
+std::vector<float> TSDFSystem::Irradiance(const std::vector<float>& points, const std::vector<float>& normals,
+                                          const std::vector<tsdf_uv_emitter>& emitters,
+                                          const std::vector<int32_t>& first, const tsdf_uv_config* cfg) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.Irradiance(points, normals, emitters, first, cfg);
+}
+
+std::vector<int32_t> TSDFSystem::PlanStops(const std::vector<float>& irradiance, int32_t candidates,
+                                           std::vector<float>* need, const std::vector<float>& weight, int max_stops,
+                                           float min_gain, std::vector<double>* gains) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.PlanStops(irradiance, candidates, need, weight, max_stops, min_gain, gains);
+}
+
 struct DistanceField TSDFSystem::DistanceField(const BoundingCube<float>& volumn, int max_dist, int min_weight,
                                                bool unknown) {
   std::unique_lock<std::mutex> lock(mtx_queue_);

@@ -73,6 +73,13 @@ class TSDFSystem {
   void AccumulateDose(const std::vector<float>& points, const std::vector<float>& normals,
                       const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
                       const tsdf_uv_config* cfg = nullptr);
+  // lamp-stop planning (TSDFGrid::Irradiance / PlanStops): wait and lock like the dose calls
+  std::vector<float> Irradiance(const std::vector<float>& points, const std::vector<float>& normals,
+                                const std::vector<tsdf_uv_emitter>& emitters, const std::vector<int32_t>& first,
+                                const tsdf_uv_config* cfg = nullptr);
+  std::vector<int32_t> PlanStops(const std::vector<float>& irradiance, int32_t candidates, std::vector<float>* need,
+                                 const std::vector<float>& weight, int max_stops = 16, float min_gain = 0.0f,
+                                 std::vector<double>* gains = nullptr);
   // the distance field of the voxels in `volumn` (TSDFGrid::DistanceField): waits and locks like the dose calls
   struct DistanceField DistanceField(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
                                      bool unknown = false);

@@ -1,9 +1,12 @@
 // uv_dose.h -- the lamp model and the dose bookkeeping around TSDFGrid::AccumulateDose (DESIGN.md "UV
-// dose"): a tube lamp as point emitters, and the dose of a re-extracted mesh carried over by vertex key.
-// Host code only (no engine call); tsdf_amd/uv.py is the same in numpy.
+// dose"): a tube lamp as point emitters, and the dose of a re-extracted mesh carried over by vertex key;
+// for the lamp-stop planner (DESIGN.md "Lamp-stop planning"; TSDFGrid::Irradiance / PlanStops) a batch of
+// candidate tubes, the missing dose, the vertex areas and the stand-off positions of a distance field.
+// Host code only (no engine call); tsdf_amd/uv.py and tsdf_amd/esdf.py are the same in numpy.
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -17,18 +20,22 @@ using UVEmitter = tsdf_uv_emitter;
 
 // A tube lamp from p0 to p1 [m] that radiated power_w for dwell_s seconds, as `segments` point
 // emitters at the midpoints of its equal segments, each with power_w * dwell_s / segments joules.
-inline std::vector<UVEmitter> tube_emitters(const float p0[3], const float p1[3], float power_w, float dwell_s,
+inline std::vector<UVEmitter> tube_emitters(const double p0[3], const double p1[3], float power_w, float dwell_s,
                                             int segments) {
   if (segments < 1) throw std::invalid_argument("tube_emitters: segments >= 1");
   std::vector<UVEmitter> out((size_t)segments);
   const double e = (double)power_w * (double)dwell_s / (double)segments;
   for (int i = 0; i < segments; ++i) {
     const double t = ((double)i + 0.5) / (double)segments;
-    out[(size_t)i] = UVEmitter{(float)((double)p0[0] + t * ((double)p1[0] - (double)p0[0])),
-                               (float)((double)p0[1] + t * ((double)p1[1] - (double)p0[1])),
-                               (float)((double)p0[2] + t * ((double)p1[2] - (double)p0[2])), (float)e};
+    out[(size_t)i] = UVEmitter{(float)(p0[0] + t * (p1[0] - p0[0])), (float)(p0[1] + t * (p1[1] - p0[1])),
+                               (float)(p0[2] + t * (p1[2] - p0[2])), (float)e};
   }
   return out;
+}
+inline std::vector<UVEmitter> tube_emitters(const float p0[3], const float p1[3], float power_w, float dwell_s,
+                                            int segments) {
+  const double a[3] = {p0[0], p0[1], p0[2]}, b[3] = {p1[0], p1[1], p1[2]};
+  return tube_emitters(a, b, power_w, dwell_s, segments);
 }
 
 // The dose of every vertex of a new extraction whose key (gx, gy, gz, axis: tsdf_mesh_out.keys, 4 per
@@ -45,6 +52,103 @@ inline std::vector<float> carry_dose(const std::vector<int32_t>& old_keys, const
     const auto it = seen.find({new_keys[4 * i], new_keys[4 * i + 1], new_keys[4 * i + 2], new_keys[4 * i + 3]});
     if (it != seen.end()) out[i] = it->second;
   }
+  return out;
+}
+
+// ---- the lamp-stop planner's inputs ----
+// Candidate lamp placements as tsdf_uv_irradiance takes them: candidate c's emitters are
+// emitters[first[c] .. first[c + 1] - 1]; first holds one offset more than there are candidates.
+struct LampCandidates {
+  std::vector<UVEmitter> emitters;
+  std::vector<int32_t> first{0};
+  int32_t size() const { return (int32_t)first.size() - 1; }
+};
+
+// One tube lamp per centre (3 floats each) [m], all along `axis` (any length, not zero) and `length` metres
+// long: tube_emitters(centre - h, centre + h, ...) with h = axis / |axis| * length / 2, in double.
+inline LampCandidates tube_candidates(const std::vector<float>& centres, const float axis[3], float length,
+                                      float power_w, float dwell_s, int segments) {
+  if (centres.size() % 3) throw std::invalid_argument("tube_candidates: 3 floats per centre");
+  if (segments < 1) throw std::invalid_argument("tube_candidates: segments >= 1");
+  const double a[3] = {axis[0], axis[1], axis[2]};
+  const double norm = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  if (!(norm > 0.0)) throw std::invalid_argument("tube_candidates: axis is zero");
+  const double half = (double)length / 2;
+  double h[3];
+  for (int k = 0; k < 3; ++k) h[k] = a[k] / norm * half;
+  LampCandidates out;
+  for (size_t c = 0; c < centres.size() / 3; ++c) {
+    double p0[3], p1[3];
+    for (int k = 0; k < 3; ++k) p0[k] = (double)centres[3 * c + k] - h[k], p1[k] = (double)centres[3 * c + k] + h[k];
+    const std::vector<UVEmitter> e = tube_emitters(p0, p1, power_w, dwell_s, segments);
+    out.emitters.insert(out.emitters.end(), e.begin(), e.end());
+    out.first.push_back((int32_t)out.emitters.size());
+  }
+  return out;
+}
+
+// What each vertex still lacks, as PlanStops takes it: max(target - dose, 0) in float where prob >=
+// prob_min (the high-touch surface), 0 elsewhere.
+inline std::vector<float> plan_need(const std::vector<float>& dose, const std::vector<float>& prob, float target,
+                                    float prob_min = 0.5f) {
+  if (dose.size() != prob.size()) throw std::invalid_argument("plan_need: one probability per dose");
+  std::vector<float> out(dose.size(), 0.0f);
+  for (size_t i = 0; i < out.size(); ++i) {
+    const float miss = target - dose[i];
+    if (prob[i] >= prob_min && miss > 0.0f) out[i] = miss;
+  }
+  return out;
+}
+
+// A third of the area [m^2] of the triangles around each vertex of an indexed mesh (3 floats per vertex,
+// 3 indices per triangle), summed in double: first every triangle's first corner in triangle order, then
+// the second corners, then the third. Meant for weight = area * prob.
+inline std::vector<float> vertex_area(const std::vector<float>& verts, const std::vector<int32_t>& tris) {
+  if (verts.size() % 3 || tris.size() % 3) throw std::invalid_argument("vertex_area: 3 values per vertex / triangle");
+  const size_t nv = verts.size() / 3, nt = tris.size() / 3;
+  std::vector<double> third(nt), acc(nv, 0.0);
+  for (size_t t = 0; t < nt; ++t) {
+    double p[3][3];
+    for (int k = 0; k < 3; ++k) {
+      const int32_t v = tris[3 * t + k];
+      if (v < 0 || (size_t)v >= nv) throw std::invalid_argument("vertex_area: vertex index out of range");
+      for (int a = 0; a < 3; ++a) p[k][a] = verts[3 * (size_t)v + a];
+    }
+    double e1[3], e2[3];
+    for (int a = 0; a < 3; ++a) e1[a] = p[1][a] - p[0][a], e2[a] = p[2][a] - p[0][a];
+    const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2],
+                 cz = e1[0] * e2[1] - e1[1] * e2[0];
+    third[t] = std::sqrt((cx * cx + cy * cy) + cz * cz) / 6.0;
+  }
+  for (int k = 0; k < 3; ++k)
+    for (size_t t = 0; t < nt; ++t) acc[(size_t)tris[3 * t + k]] += third[t];
+  std::vector<float> out(nv);
+  for (size_t i = 0; i < nv; ++i) out[i] = (float)acc[i];
+  return out;
+}
+
+// Where a lamp may stand: the world positions [m], 3 floats each, of the free voxels (state 1) of a distance
+// field (d2 and state nz * ny * nx, x fastest; tsdf_types.h DistanceField) whose clearance sqrtf(d2) * voxel
+// lies in [lo, hi] and that lie on the lattice origin + stride * k of the box, in box order. Voxel v sits at
+// v * voxel. A field built with unknown sites keeps the candidates clear of unobserved space as well.
+inline std::vector<float> standoff_candidates(const std::vector<uint16_t>& d2, const std::vector<uint8_t>& state,
+                                              const int32_t origin[3], const int32_t dims[3], float voxel, float lo,
+                                              float hi, int stride) {
+  if (stride < 1) throw std::invalid_argument("standoff_candidates: stride >= 1");
+  if (dims[0] < 0 || dims[1] < 0 || dims[2] < 0) throw std::invalid_argument("standoff_candidates: dims");
+  const size_t nvox = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];
+  if (d2.size() != nvox || state.size() != nvox)
+    throw std::invalid_argument("standoff_candidates: d2 and state hold one value per voxel of the box");
+  std::vector<float> out;
+  for (int z = 0; z < dims[2]; z += stride)
+    for (int y = 0; y < dims[1]; y += stride)
+      for (int x = 0; x < dims[0]; x += stride) {
+        const size_t i = ((size_t)z * dims[1] + y) * dims[0] + x;
+        const float d = std::sqrt((float)d2[i]) * voxel;
+        if (state[i] != 1 || !(d >= lo && d <= hi)) continue;
+        const int64_t v[3] = {(int64_t)origin[0] + x, (int64_t)origin[1] + y, (int64_t)origin[2] + z};
+        for (int a = 0; a < 3; ++a) out.push_back((float)v[a] * voxel);
+      }
   return out;
 }
 

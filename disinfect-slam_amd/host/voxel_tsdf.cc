@@ -179,6 +179,43 @@ void TSDFGrid::AccumulateDose(const std::vector<float>& points, const std::vecto
              "tsdf_uv_dose");
 }
 
+std::vector<float> TSDFGrid::Irradiance(const std::vector<float>& points, const std::vector<float>& normals,
+                                        const std::vector<tsdf_uv_emitter>& emitters, const std::vector<int32_t>& first,
+                                        const tsdf_uv_config* cfg) {
+  if (group_) throw std::runtime_error("TSDFGrid::Irradiance: not available on a sharded volume");
+  if (points.size() % 3 || normals.size() != points.size())
+    throw std::invalid_argument("TSDFGrid::Irradiance: 3 floats per point and normal");
+  if (first.empty() || first.back() < 0 || (size_t)first.back() != emitters.size())
+    throw std::invalid_argument("TSDFGrid::Irradiance: first holds one offset more than there are candidates and "
+                                "ends at the number of emitters");
+  const size_t n = points.size() / 3, C = first.size() - 1;
+  std::vector<float> out(C * n);
+  check_tsdf(tsdf_uv_irradiance(engine_, points.data(), normals.data(), (int64_t)n, emitters.data(), first.data(),
+                                (int32_t)C, cfg, out.data(), TSDF_MEM_HOST),
+             "tsdf_uv_irradiance");
+  return out;
+}
+
+std::vector<int32_t> TSDFGrid::PlanStops(const std::vector<float>& irradiance, int32_t candidates,
+                                         std::vector<float>* need, const std::vector<float>& weight, int max_stops,
+                                         float min_gain, std::vector<double>* gains) {
+  if (group_) throw std::runtime_error("TSDFGrid::PlanStops: not available on a sharded volume");
+  if (!need || candidates < 0 || max_stops < 0 || irradiance.size() != (size_t)candidates * need->size() ||
+      (!weight.empty() && weight.size() != need->size()))
+    throw std::invalid_argument("TSDFGrid::PlanStops: one row of need's length per candidate, one weight per need");
+  const tsdf_uv_plan_config c{max_stops, min_gain};
+  std::vector<int32_t> stops((size_t)max_stops);
+  std::vector<double> g((size_t)max_stops);
+  int32_t k = 0;
+  check_tsdf(tsdf_uv_plan(engine_, irradiance.data(), candidates, (int64_t)need->size(), need->data(),
+                          weight.empty() ? nullptr : weight.data(), &c, stops.data(), g.data(), &k, TSDF_MEM_HOST),
+             "tsdf_uv_plan");
+  stops.resize((size_t)k);
+  g.resize((size_t)k);
+  if (gains) *gains = g;
+  return stops;
+}
+
 struct DistanceField TSDFGrid::DistanceField(const BoundingCube<float>& volumn, int max_dist, int min_weight,
                                              bool unknown) {
   if (group_) throw std::runtime_error("TSDFGrid::DistanceField: not available on a sharded volume");

@@ -58,6 +58,19 @@ class TSDFGrid {
                       const std::vector<tsdf_uv_emitter>& emitters, std::vector<float>* dose,
                       const tsdf_uv_config* cfg = nullptr);
 
+  // Lamp-stop planning (tsdf_uv_irradiance / tsdf_uv_plan). Irradiance: the dose each of C candidates
+  // (emitters[first[c] .. first[c + 1] - 1]; first holds C + 1 offsets) alone would add to each receiver, C
+  // rows of one float per receiver. Not available on a sharded volume. PlanStops: the greedy choice of at
+  // most max_stops rows of such a matrix against the missing dose `need` (updated in place) and the
+  // weights (empty: all 1); returns the chosen candidates in order and, through gains, each round's gain.
+  // It does not touch the volume.
+  std::vector<float> Irradiance(const std::vector<float>& points, const std::vector<float>& normals,
+                                const std::vector<tsdf_uv_emitter>& emitters, const std::vector<int32_t>& first,
+                                const tsdf_uv_config* cfg = nullptr);
+  std::vector<int32_t> PlanStops(const std::vector<float>& irradiance, int32_t candidates, std::vector<float>* need,
+                                 const std::vector<float>& weight, int max_stops = 16, float min_gain = 0.0f,
+                                 std::vector<double>* gains = nullptr);
+
   // Exact Euclidean distance field (tsdf_distance_field) over the voxels whose centres lie in `volumn`
   // (voxel v's centre is v * voxel_size): squared distances [voxels^2] to the nearest surface voxel of the
   // box, saturated at max_dist^2; unknown: unobserved voxels are sites too. Pad the cube by max_dist voxels

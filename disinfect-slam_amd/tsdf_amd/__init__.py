@@ -927,8 +927,8 @@ class Engine:
 
     # ---- UV dose ----
     def _points(self, a, device, cols=3):
-        """An (n, cols) f32 array as the call takes it: a contiguous numpy array, or with device=True a
-        contiguous torch tensor on this engine's GPU."""
+        """An (n, cols) f32 array as the call takes it (cols=1: (n,); cols=None: any 2-D matrix): a
+        contiguous numpy array, or with device=True a contiguous torch tensor on this engine's GPU."""
         if device:
             import torch
             t = a if _is_torch_cuda(a) else torch.as_tensor(np.asarray(a, np.float32), device=f"cuda:{self.device}")
@@ -937,6 +937,10 @@ class Engine:
             if _is_torch_cuda(a):
                 raise ValueError("device tensors need device=True")
             t = np.ascontiguousarray(a, dtype=np.float32)
+        if cols is None:
+            if t.ndim != 2:
+                raise ValueError(f"expected a 2-D matrix, got {tuple(t.shape)}")
+            return t
         if (cols == 1 and t.ndim != 1) or (cols > 1 and (t.ndim != 2 or t.shape[1] != cols)):
             raise ValueError(f"expected shape (n{', %d' % cols if cols > 1 else ''}), got {tuple(t.shape)}")
         return t
@@ -968,15 +972,7 @@ class Engine:
         tsdf_uv_config's fields (bias, step, min_range, max_range, sample_offset, min_weight, use_grid).
         Returns the dose array, or with device=True the tensor."""
         L = _lib.load()
-        c = _lib.UvConfig()
-        L.tsdf_uv_config_default(self._h, C.byref(c))
-        for k, v in cfg.items():
-            if k in ("min_weight", "use_grid"):
-                setattr(c, k, int(v))
-            elif k in ("bias", "step", "min_range", "max_range", "sample_offset"):
-                setattr(c, k, float(v))
-            else:
-                raise TypeError(f"uv_dose: unknown option {k}")
+        c = self._uv_config("uv_dose", cfg)
         p = self._points(points, device)
         nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
         em = np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
@@ -997,6 +993,83 @@ class Engine:
         self._signal_torch(p, nr, d)
         _lib.check(rc, "tsdf_uv_dose")
         return d
+
+    def _uv_config(self, what, cfg):
+        L = _lib.load()
+        c = _lib.UvConfig()
+        L.tsdf_uv_config_default(self._h, C.byref(c))
+        for k, v in cfg.items():
+            if k in ("min_weight", "use_grid"):
+                setattr(c, k, int(v))
+            elif k in ("bias", "step", "min_range", "max_range", "sample_offset"):
+                setattr(c, k, float(v))
+            else:
+                raise TypeError(f"{what}: unknown option {k}")
+        return c
+
+    # ---- lamp-stop planning ----
+    def uv_irradiance(self, points, normals, emitters, first, device: bool = False, **cfg):
+        """The dose [J/m^2] each of C candidate lamp placements alone would add to each receiver
+        (tsdf_uv_irradiance): row c is what uv_dose writes into zeros given only emitters[first[c]:first[c + 1]],
+        bit for bit, from one call. points, normals (n, 3) f32 (normals=None: surface_normals); emitters
+        (m, 4) f32 and first (C + 1,) int32 on the host (uv.tube_candidates), first[0] == 0, non-decreasing,
+        first[-1] == m. Keywords are tsdf_uv_config's fields, as uv_dose's. Returns (C, n) f32: a numpy
+        array, or with device=True a tensor on this engine's GPU."""
+        L = _lib.load()
+        c = self._uv_config("uv_irradiance", cfg)
+        p = self._points(points, device)
+        nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
+        em = np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
+        fi = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        if tuple(nr.shape) != tuple(p.shape):
+            raise ValueError("points and normals do not match")
+        if fi.size < 1 or int(fi[-1]) != em.shape[0]:
+            raise _lib.TSDFError("tsdf_uv_irradiance: invalid argument (first holds C + 1 offsets and ends at the "
+                                 "number of emitters)")
+        n, nc = p.shape[0], fi.size - 1
+        if device:
+            import torch
+            out = torch.empty((nc, n), dtype=torch.float32, device=p.device)
+        else:
+            out = np.empty((nc, n), np.float32)
+        self._wait_torch(p, nr, out)
+        rc = L.tsdf_uv_irradiance(self._h, _ptr(p), _ptr(nr), n, _ptr(em), _ptr(fi), nc, C.byref(c), _ptr(out),
+                                  TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        self._signal_torch(p, nr, out)
+        _lib.check(rc, "tsdf_uv_irradiance")
+        return out
+
+    def uv_plan(self, irradiance, need, weight=None, max_stops: int = 16, min_gain: float = 0.0,
+                device: bool = False):
+        """Greedy lamp stops on a (C, n) irradiance matrix (tsdf_uv_plan): each round picks the candidate that
+        removes the most weighted missing dose, sum over i of weight[i] * min(E[c][i], need[i]) (the lowest
+        index between equal gains), and subtracts its row from need, until max_stops rounds ran or the best
+        gain is not positive or below min_gain. need (n,) f32 [J/m^2] (uv.plan_need), weight (n,) f32 or None
+        for all 1 (uv.vertex_area * prob). Deterministic: the same inputs give the same bits. Returns
+        dict(stops (k,) int32, gains (k,) f64, need (n,) f32: what is still missing after the stops); need is
+        a new array, or with device=True a new tensor (irradiance and need may be tensors then)."""
+        L = _lib.load()
+        E = self._points(irradiance, device, cols=None)
+        nc, n = int(E.shape[0]), int(E.shape[1])
+        if device:
+            nd = self._points(need, device, cols=1).clone()
+        else:
+            nd = np.array(need, dtype=np.float32, order="C", copy=True)
+            if nd.ndim != 1:
+                raise ValueError("need: expected shape (n,)")
+        w = None if weight is None else self._points(weight, device, cols=1)
+        if nd.shape[0] != n or (w is not None and w.shape[0] != n):
+            raise ValueError("irradiance, need and weight do not match")
+        c = _lib.UvPlanConfig(int(max_stops), float(min_gain))
+        k = max(int(max_stops), 0)
+        stops, gains, num = np.zeros(k, np.int32), np.zeros(k, np.float64), C.c_int32(0)
+        arrs = (E, nd) if w is None else (E, nd, w)
+        self._wait_torch(*arrs)
+        rc = L.tsdf_uv_plan(self._h, _ptr(E), nc, n, _ptr(nd), _ptr(w), C.byref(c), _ptr(stops), _ptr(gains),
+                            C.byref(num), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        self._signal_torch(*arrs)
+        _lib.check(rc, "tsdf_uv_plan")
+        return dict(stops=stops[:num.value].copy(), gains=gains[:num.value].copy(), need=nd)
 
     # ---- distance field ----
     def distance_field(self, origin, dims, max_dist: int = 255, min_weight: int = 1, unknown: bool = False,

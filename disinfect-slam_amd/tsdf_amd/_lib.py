@@ -174,6 +174,10 @@ class UvConfig(C.Structure):
     ]
 
 
+class UvPlanConfig(C.Structure):
+    _fields_ = [("max_stops", C.c_int32), ("min_gain", C.c_float)]
+
+
 class EdtConfig(C.Structure):
     _fields_ = [
         ("origin", C.c_int32 * 3),
@@ -214,6 +218,7 @@ EXPORTS = [
     "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track_config_default", "tsdf_track",
     "tsdf_uv_config_default", "tsdf_surface_normals", "tsdf_uv_dose",
     "tsdf_edt_config_default", "tsdf_distance_field",
+    "tsdf_uv_irradiance", "tsdf_uv_plan_config_default", "tsdf_uv_plan",
 ]
 
 _lib = None
@@ -300,6 +305,10 @@ def load(path: str | None = None):
     L.tsdf_uv_config_default.restype = None
     L.tsdf_surface_normals.argtypes = [P, P, i64, f, P, i]
     L.tsdf_uv_dose.argtypes = [P, P, P, i64, P, C.c_int32, C.POINTER(UvConfig), P, i]
+    L.tsdf_uv_irradiance.argtypes = [P, P, P, i64, P, P, C.c_int32, C.POINTER(UvConfig), P, i]
+    L.tsdf_uv_plan_config_default.argtypes = [C.POINTER(UvPlanConfig)]
+    L.tsdf_uv_plan_config_default.restype = None
+    L.tsdf_uv_plan.argtypes = [P, P, C.c_int32, i64, P, P, C.POINTER(UvPlanConfig), P, P, C.POINTER(C.c_int32), i]
     L.tsdf_edt_config_default.argtypes = [C.POINTER(EdtConfig)]
     L.tsdf_edt_config_default.restype = None
     L.tsdf_distance_field.argtypes = [P, C.POINTER(EdtConfig), C.POINTER(EdtOut)]
@@ -350,7 +359,8 @@ def load(path: str | None = None):
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
-                 "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field"):
+                 "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
+                 "tsdf_uv_irradiance", "tsdf_uv_plan"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -65,3 +65,22 @@ def clearance(field, voxel: float, points, sample_offset: float = 0.0):
     else:
         st = np.asarray(field["state"])[v[:, 2], v[:, 1], v[:, 0]]
     return dist, np.where(ok, st, 0).astype(np.uint8)
+
+
+def standoff_candidates(field, voxel: float, lo: float, hi: float, stride: int) -> np.ndarray:
+    """Where a lamp may stand: the world positions [m] (k, 3) f32 of the free voxels (state 1) of a
+    distance_field result whose clearance metres() lies in [lo, hi] and that lie on the lattice origin +
+    stride * k of the box, in box order (z slowest, x fastest). Voxel v sits at v * voxel. With a field built
+    with unknown=True unobserved space is a site, so the clearance is to it as well and no candidate
+    stands in or next to it."""
+    if field.get("state") is None:
+        raise ValueError("standoff_candidates: the field has no state (distance_field(..., state=True))")
+    if stride < 1:
+        raise ValueError("standoff_candidates: stride >= 1")
+    d = metres(field, voxel)
+    ok = (np.asarray(field["state"]) == 1) & (d >= np.float32(lo)) & (d <= np.float32(hi))
+    lat = np.zeros(ok.shape, bool)
+    lat[::stride, ::stride, ::stride] = True
+    z, y, x = np.nonzero(ok & lat)
+    v = np.stack([x, y, z], -1).astype(np.int64) + np.asarray(field["origin"], np.int64)
+    return (v.astype(np.float32) * np.float32(voxel)).astype(np.float32)

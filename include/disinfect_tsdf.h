@@ -574,6 +574,54 @@ int tsdf_uv_dose(tsdf_engine* e, const float* points, const float* normals, int6
                  const tsdf_uv_emitter* emitters /* host */, int32_t m, const tsdf_uv_config* cfg /* NULL = defaults */,
                  float* dose /* n, in/out [J/m^2] */, int mem_kind /* points, normals, dose alike */);
 
+/* ---- Lamp-stop planning: batched irradiance and a greedy choice of stops (no reference counterpart) ----
+ * tsdf_uv_irradiance: the dose each of C candidate lamp placements alone would add to each of n receivers,
+ * as a C x n matrix from one call. Candidate c's emitters are emitters[first[c] .. first[c + 1] - 1];
+ * first holds C + 1 offsets and first[C] is the number of emitters the caller's array holds.
+ * out[c * n + i] is exactly the acc of tsdf_uv_dose above for receiver i over candidate c's emitters in that
+ * order: the bytes tsdf_uv_dose writes into a zero dose given only those emitters. A zero normal gives 0; a
+ * candidate that is empty, out of range or fully shadowed gives a row of zeros. The answer does not depend
+ * on use_grid, on the other candidates of the batch or on mem_kind. Required: first[0] == 0, first
+ * non-decreasing, and tsdf_uv_dose's conditions on the configuration; anything else is
+ * TSDF_ERR_INVALID_ARG. n == 0 or C == 0 is TSDF_OK with nothing written. Like the dose calls it completes a
+ * pending pipelined frame first, runs asynchronously on the engine stream for device memory and copies for
+ * host memory, refuses a shard engine, only reads the volume and sets no status bits. C * n may pass 2^31.
+ *
+ * tsdf_uv_plan: greedy selection on such a matrix E. need[i] is the dose receiver i still lacks, weight[i]
+ * what a joule per square metre is worth there (e.g. vertex area * touch probability; finite and >= 0).
+ * Rounds r = 0, 1, ... run while r < max_stops. In fp32, one operation at a time:
+ *   g(c, i) = E[c][i] > 0 && need[i] > 0 ? weight[i] * fminf(E[c][i], need[i]) : 0
+ * -- for every input that is not a NaN this is t = fminf(E[c][i], need[i]), g = t > 0 ? weight[i] * t : 0;
+ * written with both tests a NaN in E or need contributes nothing, where fminf alone would hand its partner
+ * through. G[c] is the sum of g(c, i) over i in double, by a fixed addition tree that depends on n only (no
+ * atomics; the same in every round and for every candidate; DESIGN.md "Lamp-stop planning" gives it). b is
+ * the lowest c with the largest G[c]. The loop stops when !(G[b] > 0) || !(G[b] >= min_gain). Otherwise
+ * stops[r] = b, gains[r] = G[b], and in fp32 need[i] = fmaxf(need[i] - E[b][i], 0) for the entries with
+ * E[b][i] > 0; every other entry stays as it is. A candidate may be picked again (a longer dwell). The same
+ * inputs give the same stops, gains and need, bit for bit.
+ * *num_stops is the number of rounds that chose a stop; entries of stops / gains past it are not written.
+ * C == 0, n == 0 or max_stops == 0 is TSDF_OK with *num_stops = 0. Required: 0 <= max_stops <= 65536,
+ * min_gain not a NaN. irradiance, need and weight are mem_kind memory alike; stops, gains and num_stops are
+ * host memory, and the call returns after one synchronisation of the engine stream (no read per round).
+ * It does not touch the volume: the engine lends its stream and scratch (grown on demand, freed by
+ * tsdf_destroy), pending frames stay pending, and a shard engine (shard_count > 1) serves as well as any
+ * other. */
+int tsdf_uv_irradiance(tsdf_engine* e, const float* points, const float* normals, int64_t n,
+                       const tsdf_uv_emitter* emitters /* host, all candidates concatenated */,
+                       const int32_t* first /* host, C + 1 offsets into emitters */, int32_t C,
+                       const tsdf_uv_config* cfg /* NULL = defaults */,
+                       float* out /* C x n, row-major: row c = candidate c */, int mem_kind);
+typedef struct tsdf_uv_plan_config {
+  int32_t max_stops; /* rounds at most */
+  float min_gain;    /* a round whose best gain is below this ends the plan */
+} tsdf_uv_plan_config;
+/* max_stops 16, min_gain 0 */
+void tsdf_uv_plan_config_default(tsdf_uv_plan_config* cfg);
+int tsdf_uv_plan(tsdf_engine* e, const float* irradiance /* C x n */, int32_t C, int64_t n,
+                 float* need /* n, in/out [J/m^2] */, const float* weight /* n, NULL = all 1 */,
+                 const tsdf_uv_plan_config* cfg /* NULL = defaults */, int32_t* stops /* host, max_stops */,
+                 double* gains /* host, max_stops */, int32_t* num_stops /* host */, int mem_kind);
+
 /* ---- Euclidean distance field over a box of the volume (no reference counterpart) ----
  * The exact squared Euclidean distance, in voxels, from every voxel of a box to the nearest surface
  * voxel of the volume -- the layer a planner asks for clearance, which the TSDF only knows inside its
