@@ -302,6 +302,11 @@ struct tsdf_engine {
   // distance field (tsdf_distance_field): the site bitmap, the x pass's bytes, the y pass's u16 and, for
   // host outputs, their staging, one section each (tsdf_host_edt.hip). Grow-only.
   DevBuf<uint8_t> edt_buf;
+  // travel field (tsdf_travel_field / tsdf_travel_paths; tsdf_host_travel.hip): the round control words, the
+  // tiles' wake-up stamps, the two tile lists, the seeds and, for host arrays, their staging, one section
+  // each; or a paths call's targets, lengths and paths. Grow-only. (Last: the frame path's fields keep
+  // their offsets.)
+  DevBuf<uint8_t> tv_buf;
 
   tsdf_engine() = default;
   // D's buffers, the pinned mirrors, events and streams; the scratch above frees itself. The caller has

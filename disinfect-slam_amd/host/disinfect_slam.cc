@@ -1,6 +1,8 @@
 // disinfect_slam.cc -- DISINFSystem's TSDF half (disinfect_slam/disinfect_slam.cc:3-116).
 #include "disinfect_slam.h"
 
+#include <algorithm>
+#include <cmath>
 #include <limits>
 #include <stdexcept>
 
@@ -61,6 +63,18 @@ TriMesh DISINFSystem::query_mesh(const BoundingCube<float>& volumn) { return TSD
 DistanceField DISINFSystem::query_distance_field(const BoundingCube<float>& volumn, int max_dist, int min_weight,
                                                  bool unknown) {
   return TSDF_->DistanceField(volumn, max_dist, min_weight, unknown);
+}
+
+TravelField DISINFSystem::query_travel_field(const DistanceField& field, const std::vector<float>& from_world,
+                                             float clearance_m, bool unknown_free) {
+  if (from_world.size() % 3) throw std::invalid_argument("DISINFSystem::query_travel_field: 3 floats per position");
+  const float voxel = TSDF_->voxel_size();
+  std::vector<int32_t> seeds(from_world.size());
+  for (size_t i = 0; i < seeds.size(); ++i) seeds[i] = nearest_voxel(from_world[i], voxel);
+  // sqrt(d2) * voxel >= clearance_m
+  const double q = std::max((double)clearance_m, 0.0) / (double)voxel;
+  const int clearance2 = (int)std::min(std::ceil(q * q), 65025.0);
+  return TSDF_->TravelField(field, seeds, clearance2, unknown_free);
 }
 
 void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {

@@ -63,6 +63,14 @@ class DISINFSystem {
   // state (TSDFGrid::DistanceField). unknown: never-observed space is an obstacle as well.
   DistanceField query_distance_field(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
                                      bool unknown = false);
+  // Whether and how far a lamp travels to reach the voxels of such a field: the travel field
+  // (TSDFGrid::TravelField) flooded from the voxel nearest to each world position of from_world (3 floats
+  // each, e.g. where the arm is now) through voxels at least clearance_m metres from every surface voxel
+  // that are observed free or, with unknown_free, never observed (the optimistic planner: an unobserved
+  // gap in a wall leaks). reachable_candidates (uv_dose.h) filters standoff_candidates with it;
+  // tsdf().TravelPaths gives the way to a chosen stop.
+  TravelField query_travel_field(const DistanceField& field, const std::vector<float>& from_world,
+                                 float clearance_m = 0.0f, bool unknown_free = false);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

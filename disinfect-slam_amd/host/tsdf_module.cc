@@ -138,6 +138,22 @@ struct DistanceField TSDFSystem::DistanceField(const BoundingCube<float>& volumn
   return tsdf_.DistanceField(volumn, max_dist, min_weight, unknown);
 }
 
+struct TravelField TSDFSystem::TravelField(const struct DistanceField& field, const std::vector<int32_t>& seeds,
+                                           int clearance2, bool unknown_free) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.TravelField(field, seeds, clearance2, unknown_free);
+}
+
+std::vector<std::vector<int32_t>> TSDFSystem::TravelPaths(const struct TravelField& travel,
+                                                          const std::vector<int32_t>& targets, int max_len) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.TravelPaths(travel, targets, max_len);
+}
+
 void TSDFSystem::ImportBlocks(const void* records, int64_t n, bool replace) {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });

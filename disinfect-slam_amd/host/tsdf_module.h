@@ -83,6 +83,13 @@ class TSDFSystem {
   // the distance field of the voxels in `volumn` (TSDFGrid::DistanceField): waits and locks like the dose calls
   struct DistanceField DistanceField(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
                                      bool unknown = false);
+  // the travel field over a distance field's box and the paths back (TSDFGrid::TravelField / TravelPaths):
+  // wait and lock like the distance field
+  struct TravelField TravelField(const struct DistanceField& field, const std::vector<int32_t>& seeds,
+                                 int clearance2 = 0, bool unknown_free = false);
+  std::vector<std::vector<int32_t>> TravelPaths(const struct TravelField& travel, const std::vector<int32_t>& targets,
+                                                int max_len = 4096);
+  float voxel_size() const { return tsdf_.voxel_size(); }
   // the volume replaced by (replace) or extended with n block records (tsdf_import_blocks, host memory;
   // one unsharded volume only), after every queued frame
   void ImportBlocks(const void* records, int64_t n, bool replace);

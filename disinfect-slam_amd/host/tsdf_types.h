@@ -248,6 +248,18 @@ struct DistanceField {
   }
 };
 
+// The travel field over a distance field's box (tsdf_travel_field): the least <3, 4, 5> chamfer cost from the
+// seeds to every voxel through passable voxels, 0 at the seeds, TSDF_TRAVEL_UNREACHED where no path exists;
+// cost / 3 is a length in voxels. Voxel (x, y, z) of the box is global voxel origin + (x, y, z).
+struct TravelField {
+  int32_t origin[3] = {0, 0, 0};
+  int32_t dims[3] = {0, 0, 0};  // nx, ny, nz
+  std::vector<uint32_t> cost;   // nz * ny * nx, x fastest
+  int32_t seeded = 0;           // seeds used: inside the box and passable
+  int32_t rounds = 0;           // relaxation rounds the call ran
+  size_t at(int x, int y, int z) const { return ((size_t)z * dims[1] + y) * dims[0] + x; }
+};
+
 // The pose of a depth frame against the volume (tsdf_track). degenerate: too few correspondences
 // or singular normal equations; pose is then the last good estimate (the guess when none was made).
 struct TrackResult {

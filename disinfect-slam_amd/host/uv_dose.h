@@ -5,6 +5,7 @@
 // Host code only (no engine call); tsdf_amd/uv.py and tsdf_amd/esdf.py are the same in numpy.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -149,6 +150,57 @@ inline std::vector<float> standoff_candidates(const std::vector<uint16_t>& d2, c
         const int64_t v[3] = {(int64_t)origin[0] + x, (int64_t)origin[1] + y, (int64_t)origin[2] + z};
         for (int a = 0; a < 3; ++a) out.push_back((float)v[a] * voxel);
       }
+  return out;
+}
+
+// ---- travel field (tsdf_types.h TravelField; tsdf_amd.esdf's helpers of the same names) ----
+// The library's nearest voxel of a world coordinate: round(p / voxel - sample_offset) in float, half away
+// from zero; 0 for a NaN.
+inline int32_t nearest_voxel(float p, float voxel, float sample_offset = 0.0f) {
+  const float f = p / voxel - sample_offset;
+  if (!(f == f) || std::fabs(f) < 0.5f) return 0;
+  const float r = std::trunc(f + std::copysign(0.5f, f));
+  return (int32_t)std::min(std::max((double)r, -2147483648.0), 2147483647.0);
+}
+
+// cost / 3 * voxel [m] for every voxel of a travel field: the travel distance from the nearest seed,
+// infinity where unreached.
+inline std::vector<float> travel_metres(const std::vector<uint32_t>& cost, float voxel) {
+  std::vector<float> out(cost.size());
+  for (size_t i = 0; i < cost.size(); ++i)
+    out[i] = cost[i] == TSDF_TRAVEL_UNREACHED ? INFINITY : ((float)cost[i] / 3.0f) * voxel;
+  return out;
+}
+
+// The positions (3 floats each, e.g. standoff_candidates' output) whose nearest voxel a travel field (cost
+// nz * ny * nx, x fastest, over the box origin / dims) reached, within max_travel metres, in their order;
+// travel, when given, receives each kept position's travel distance [m]. A position outside the box is
+// unreachable.
+inline std::vector<float> reachable_candidates(const std::vector<float>& positions, const std::vector<uint32_t>& cost,
+                                               const int32_t origin[3], const int32_t dims[3], float voxel,
+                                               float max_travel = INFINITY, float sample_offset = 0.0f,
+                                               std::vector<float>* travel = nullptr) {
+  if (positions.size() % 3) throw std::invalid_argument("reachable_candidates: 3 floats per position");
+  if (dims[0] < 0 || dims[1] < 0 || dims[2] < 0 ||
+      cost.size() != (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2])
+    throw std::invalid_argument("reachable_candidates: one cost per voxel of the box");
+  std::vector<float> out;
+  if (travel) travel->clear();
+  for (size_t i = 0; i + 2 < positions.size(); i += 3) {
+    int64_t v[3];
+    bool in = true;
+    for (int a = 0; a < 3; ++a) {
+      v[a] = (int64_t)nearest_voxel(positions[i + a], voxel, sample_offset) - origin[a];
+      in = in && v[a] >= 0 && v[a] < dims[a];
+    }
+    if (!in) continue;
+    const uint32_t c = cost[((size_t)v[2] * dims[1] + (size_t)v[1]) * dims[0] + (size_t)v[0]];
+    if (c == TSDF_TRAVEL_UNREACHED) continue;
+    const float m = ((float)c / 3.0f) * voxel;
+    if (!(m <= max_travel)) continue;
+    out.insert(out.end(), positions.begin() + i, positions.begin() + i + 3);
+    if (travel) travel->push_back(m);
+  }
   return out;
 }
 

@@ -1,7 +1,9 @@
 // voxel_tsdf.cc -- TSDFGrid facade over include/disinfect_tsdf.h.
 #include "voxel_tsdf.h"
 
+#include <algorithm>
 #include <stdexcept>
+#include <string>
 
 namespace disinfect {
 
@@ -244,6 +246,76 @@ struct DistanceField TSDFGrid::DistanceField(const BoundingCube<float>& volumn, 
   out.mem_kind = TSDF_MEM_HOST;
   check_tsdf(tsdf_distance_field(engine_, &c, &out), "tsdf_distance_field");
   return f;
+}
+
+namespace {
+// global voxel triples as box-local ones, kept in int32
+std::vector<int32_t> box_local(const std::vector<int32_t>& v, const int32_t origin[3], const char* what) {
+  if (v.size() % 3) throw std::invalid_argument(std::string(what) + ": three coordinates per voxel");
+  std::vector<int32_t> out(v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    const int64_t d = (int64_t)v[i] - origin[i % 3];
+    out[i] = (int32_t)std::min<int64_t>(std::max<int64_t>(d, -((int64_t)1 << 30)), (int64_t)1 << 30);
+  }
+  return out;
+}
+}  // namespace
+
+struct TravelField TSDFGrid::TravelField(const struct DistanceField& field, const std::vector<int32_t>& seeds,
+                                         int clearance2, bool unknown_free) {
+  if (group_) throw std::runtime_error("TSDFGrid::TravelField: not available on a sharded volume");
+  struct TravelField t;
+  tsdf_travel_config c;
+  tsdf_travel_config_default(&c);
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    t.origin[a] = field.origin[a];
+    c.dims[a] = t.dims[a] = field.dims[a];
+    n *= (size_t)std::max(field.dims[a], 0);
+  }
+  if (n == 0 || field.d2.size() != n || field.state.size() != n)
+    throw std::invalid_argument("TSDFGrid::TravelField: the field needs d2 and state for every voxel of its box");
+  c.clearance2 = clearance2;
+  c.unknown_free = unknown_free ? 1 : 0;
+  const std::vector<int32_t> s = box_local(seeds, field.origin, "TSDFGrid::TravelField");
+  t.cost.resize(n);
+  check_tsdf(tsdf_travel_field(engine_, &c, field.d2.data(), field.state.data(), s.empty() ? nullptr : s.data(),
+                               (int32_t)(s.size() / 3), t.cost.data(), TSDF_MEM_HOST, &t.seeded, &t.rounds),
+             "tsdf_travel_field");
+  return t;
+}
+
+std::vector<std::vector<int32_t>> TSDFGrid::TravelPaths(const struct TravelField& travel,
+                                                        const std::vector<int32_t>& targets, int max_len) {
+  if (group_) throw std::runtime_error("TSDFGrid::TravelPaths: not available on a sharded volume");
+  const std::vector<int32_t> t = box_local(targets, travel.origin, "TSDFGrid::TravelPaths");
+  const int32_t T = (int32_t)(t.size() / 3);
+  std::vector<std::vector<int32_t>> out((size_t)T);
+  if (T == 0) return out;
+  if (travel.dims[0] < 1 || travel.dims[1] < 1 || travel.dims[2] < 1 ||
+      travel.cost.size() != (size_t)travel.dims[0] * (size_t)travel.dims[1] * (size_t)travel.dims[2])
+    throw std::invalid_argument("TSDFGrid::TravelPaths: one cost per voxel of the box");
+  int32_t cap = std::min(std::max(max_len, 1), 1 << 28);
+  for (int32_t k0 = 0; k0 < T;) {
+    const int32_t n = std::min(T - k0, std::max((1 << 28) / cap, 1));  // (a call takes T * max_len <= 2^28)
+    std::vector<int32_t> path((size_t)n * cap), len((size_t)n);
+    check_tsdf(tsdf_travel_paths(engine_, travel.dims, travel.cost.data(), TSDF_MEM_HOST, t.data() + 3 * (size_t)k0, n, cap,
+                                 path.data(), len.data()),
+               "tsdf_travel_paths");
+    int32_t longest = 0;
+    for (int32_t l : len) {
+      if (l < 0) throw std::invalid_argument("TSDFGrid::TravelPaths: a voxel without a predecessor (not a travel field)");
+      longest = std::max(longest, l);
+    }
+    if (longest > cap) {  // (ask again, with fewer targets per call if need be)
+      cap = longest;
+      continue;
+    }
+    for (int32_t k = 0; k < n; ++k)
+      out[(size_t)(k0 + k)].assign(path.begin() + (size_t)k * cap, path.begin() + (size_t)k * cap + len[(size_t)k]);
+    k0 += n;
+  }
+  return out;
 }
 
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {

@@ -79,6 +79,18 @@ class TSDFGrid {
   struct DistanceField DistanceField(const BoundingCube<float>& volumn, int max_dist = 255, int min_weight = 1,
                                      bool unknown = false);
 
+  // Travel field (tsdf_travel_field) over a distance field's box: the least travel cost from the seeds (global
+  // voxel coordinates, 3 each) through voxels with d2 >= clearance2 that are observed free or, with
+  // unknown_free, unobserved. TravelPaths (tsdf_travel_paths): the walk from each target (global voxel
+  // coordinates, 3 each) back to a seed as box-local linear indices, target first; empty for a target
+  // outside the box or unreached; asks again while a path is longer than max_len. Neither touches the
+  // volume. Not available on a sharded volume, like the distance field they start from.
+  struct TravelField TravelField(const struct DistanceField& field, const std::vector<int32_t>& seeds,
+                                 int clearance2 = 0, bool unknown_free = false);
+  std::vector<std::vector<int32_t>> TravelPaths(const struct TravelField& travel, const std::vector<int32_t>& targets,
+                                                int max_len = 4096);
+  float voxel_size() const { return voxel_size_; }
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

@@ -1111,6 +1111,111 @@ class Engine:
         _lib.check(rc, "tsdf_distance_field")
         return dict(d2=d2, state=st, origin=tuple(o), dims=tuple(d), max_dist=int(max_dist), unknown=bool(unknown))
 
+    # ---- travel field ----
+    def _box_array(self, a, dtype, shape, device, what):
+        """A field array of the box as a call takes it: contiguous numpy, or with device=True a contiguous
+        tensor on this engine's GPU (a host array is uploaded)."""
+        if device:
+            import torch
+            tdt = {np.uint16: torch.uint16, np.uint8: torch.uint8, np.uint32: torch.uint32}[dtype]
+            t = a if _is_torch_cuda(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=dtype),
+                                                            device=f"cuda:{self.device}")
+            if t.dtype != tdt:
+                raise ValueError(f"{what}: expected dtype {tdt}")
+            t = t.contiguous()
+        else:
+            if _is_torch_cuda(a):
+                t = a.cpu().numpy()
+            else:
+                t = a
+            t = np.ascontiguousarray(t, dtype=dtype)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def travel_field(self, field, seeds, clearance2: int = 0, unknown_free: bool = False, device: bool = False):
+        """The least travel cost from the seed voxels to every voxel of a distance field's box through
+        passable voxels (tsdf_travel_field). field: a distance_field result that has state. A voxel is
+        passable when d2 >= clearance2 and its state is 1 (observed free) or, with unknown_free, 0
+        (unobserved: the optimistic planner -- an unobserved gap in a wall leaks). Steps go to the 26
+        neighbours and cost 3 / 4 / 5 (face / edge / corner), so cost / 3 is a length in voxels;
+        clearance2 >= 4 keeps a diagonal step from slipping between two surface voxels that touch at a
+        corner. seeds: (S, 3) global voxel coordinates (esdf.voxel_of); seeds outside the box or impassable
+        are ignored. Returns dict(cost (nz, ny, nx) uint32: 0 at the seeds, 0xFFFFFFFF where unreached,
+        origin, dims, seeded: seeds used, rounds: relaxation rounds run): numpy, or with device=True a torch
+        tensor on this engine's GPU, ordered after the call on torch's current stream. Does not touch the
+        volume: pending frames stay pending, and a shard engine serves as well."""
+        L = _lib.load()
+        if field.get("state") is None:
+            raise ValueError("travel_field: the field has no state (distance_field(..., state=True))")
+        d = [int(v) for v in field["dims"]]
+        o = [int(v) for v in field["origin"]]
+        shape = (d[2], d[1], d[0])
+        d2 = self._box_array(field["d2"], np.uint16, shape, device, "d2")
+        st = self._box_array(field["state"], np.uint8, shape, device, "state")
+        s = np.ascontiguousarray(np.asarray(seeds, np.int64).reshape(-1, 3) - np.asarray(o, np.int64))
+        s = np.ascontiguousarray(np.clip(s, -(1 << 30), 1 << 30).astype(np.int32))
+        c = _lib.TravelConfig()
+        L.tsdf_travel_config_default(C.byref(c))
+        c.dims = (C.c_int32 * 3)(*d)
+        c.clearance2, c.unknown_free = int(clearance2), 1 if unknown_free else 0
+        if device:
+            import torch
+            cost = torch.empty(shape, dtype=torch.uint32, device=f"cuda:{self.device}")
+        else:
+            cost = np.empty(shape, np.uint32)
+        seeded, rounds = C.c_int32(0), C.c_int32(0)
+        self._wait_torch(d2, st, cost)
+        rc = L.tsdf_travel_field(self._h, C.byref(c), _ptr(d2), _ptr(st), _ptr(s) if s.shape[0] else None,
+                                 int(s.shape[0]), _ptr(cost), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST,
+                                 C.byref(seeded), C.byref(rounds))
+        self._signal_torch(d2, st, cost)
+        _lib.check(rc, "tsdf_travel_field")
+        return dict(cost=cost, origin=tuple(o), dims=tuple(d), seeded=seeded.value, rounds=rounds.value)
+
+    def travel_paths(self, travel, targets, max_len: int = 4096):
+        """The path from each target back to a seed over a travel_field result (tsdf_travel_paths): a list
+        of int32 arrays of box-local linear voxel indices (z * ny + y) * nx + x, the target first and the
+        seed last (esdf.path_points turns them into world positions). targets: (T, 3) global voxel
+        coordinates. An unreached target or one outside the box gives an empty array. Asks again with a
+        longer max_len when a path was truncated. A field this library did not write may have no
+        predecessor somewhere: ValueError."""
+        L = _lib.load()
+        d = [int(v) for v in travel["dims"]]
+        cost = travel["cost"]
+        device = _is_torch_cuda(cost)
+        if not device:
+            cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        elif not cost.is_contiguous():
+            cost = cost.contiguous()
+        if tuple(cost.shape) != (d[2], d[1], d[0]):
+            raise ValueError("travel_paths: cost does not match dims")
+        t = np.asarray(targets, np.int64).reshape(-1, 3) - np.asarray(travel["origin"], np.int64)
+        t = np.ascontiguousarray(np.clip(t, -(1 << 30), 1 << 30).astype(np.int32))
+        nt = int(t.shape[0])
+        if nt == 0:
+            return []
+        dims = (C.c_int32 * 3)(*d)
+        max_len = min(max(int(max_len), 1), 1 << 28)
+        out, k0 = [], 0
+        while k0 < nt:
+            n = min(nt - k0, max((1 << 28) // max_len, 1))  # (a call takes T * max_len <= 2^28)
+            tk = np.ascontiguousarray(t[k0:k0 + n])
+            path, ln = np.zeros((n, max_len), np.int32), np.zeros(n, np.int32)
+            self._wait_torch(cost)
+            rc = L.tsdf_travel_paths(self._h, dims, _ptr(cost), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST,
+                                     _ptr(tk), n, max_len, _ptr(path), _ptr(ln))
+            self._signal_torch(cost)
+            _lib.check(rc, "tsdf_travel_paths")
+            if (ln < 0).any():
+                raise ValueError("travel_paths: the field has a voxel without a predecessor (not a travel_field result)")
+            if int(ln.max()) > max_len:  # (a path visits a voxel once: at most 2^28, one target per call then)
+                max_len = int(ln.max())
+                continue
+            out += [path[k, :ln[k]].copy() for k in range(n)]
+            k0 += n
+        return out
+
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()
         b = None if bounds is None else np.ascontiguousarray(

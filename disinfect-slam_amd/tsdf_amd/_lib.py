@@ -195,6 +195,13 @@ class EdtOut(C.Structure):
 TSDF_EDT_SURFACE = 1
 TSDF_EDT_UNKNOWN = 2
 
+
+class TravelConfig(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("clearance2", C.c_int32), ("unknown_free", C.c_int32)]
+
+
+TSDF_TRAVEL_UNREACHED = 0xFFFFFFFF
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -219,6 +226,7 @@ EXPORTS = [
     "tsdf_uv_config_default", "tsdf_surface_normals", "tsdf_uv_dose",
     "tsdf_edt_config_default", "tsdf_distance_field",
     "tsdf_uv_irradiance", "tsdf_uv_plan_config_default", "tsdf_uv_plan",
+    "tsdf_travel_config_default", "tsdf_travel_field", "tsdf_travel_paths",
 ]
 
 _lib = None
@@ -312,6 +320,11 @@ def load(path: str | None = None):
     L.tsdf_edt_config_default.argtypes = [C.POINTER(EdtConfig)]
     L.tsdf_edt_config_default.restype = None
     L.tsdf_distance_field.argtypes = [P, C.POINTER(EdtConfig), C.POINTER(EdtOut)]
+    L.tsdf_travel_config_default.argtypes = [C.POINTER(TravelConfig)]
+    L.tsdf_travel_config_default.restype = None
+    L.tsdf_travel_field.argtypes = [P, C.POINTER(TravelConfig), P, P, P, C.c_int32, P, i, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32)]
+    L.tsdf_travel_paths.argtypes = [P, C.POINTER(C.c_int32), P, i, P, C.c_int32, C.c_int32, P, P]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -360,7 +373,7 @@ def load(path: str | None = None):
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
                  "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
-                 "tsdf_uv_irradiance", "tsdf_uv_plan"):
+                 "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

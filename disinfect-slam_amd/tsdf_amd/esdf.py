@@ -84,3 +84,41 @@ def standoff_candidates(field, voxel: float, lo: float, hi: float, stride: int) 
     z, y, x = np.nonzero(ok & lat)
     v = np.stack([x, y, z], -1).astype(np.int64) + np.asarray(field["origin"], np.int64)
     return (v.astype(np.float32) * np.float32(voxel)).astype(np.float32)
+
+
+# ---- travel field (Engine.travel_field; DESIGN.md "Travel field") ----
+# A travel is the dict Engine.travel_field returns (host arrays): cost (nz, ny, nx) uint32, 0xFFFFFFFF where
+# unreached, origin, dims. These filter the output of standoff_candidates before tubes are built.
+UNREACHED = 0xFFFFFFFF
+
+
+def travel_metres(travel, voxel: float) -> np.ndarray:
+    """cost / 3 * voxel as float32: the travel distance from the nearest seed, inf where unreached."""
+    c = np.asarray(travel["cost"])
+    m = (c.astype(np.float32) / np.float32(3)) * np.float32(voxel)
+    return np.where(c == UNREACHED, np.float32(np.inf), m).astype(np.float32)
+
+
+def reachable(travel, voxel: float, positions, max_travel=None, sample_offset: float = 0.0):
+    """(mask bool (n,), travel [m] float32 (n,)) at the voxel nearest to each world position (voxel_of):
+    whether it was reached, within max_travel metres when that is given, and how far it is from the nearest
+    seed (inf where unreached). A position outside the box is unreachable."""
+    v = voxel_of(positions, voxel, sample_offset) - np.asarray(travel["origin"], np.int64)
+    nx, ny, nz = travel["dims"]
+    ok = np.all((v >= 0) & (v < np.array([nx, ny, nz])), axis=1)
+    v = np.where(ok[:, None], v, 0)
+    c = np.asarray(travel["cost"])[v[:, 2], v[:, 1], v[:, 0]]
+    ok = ok & (c != UNREACHED)
+    m = np.where(ok, (c.astype(np.float32) / np.float32(3)) * np.float32(voxel), np.float32(np.inf)).astype(np.float32)
+    if max_travel is not None:
+        ok = ok & (m <= np.float32(max_travel))
+    return ok, m
+
+
+def path_points(travel, voxel: float, path) -> np.ndarray:
+    """World positions [m] (k, 3) f32 of a path of Engine.travel_paths (box-local linear indices, target
+    first), in travel order: the seed first, the target last. Voxel v sits at v * voxel."""
+    p = np.asarray(path, np.int64).reshape(-1)[::-1]
+    nx, ny, _ = travel["dims"]
+    v = np.stack([p % nx, p // nx % ny, p // (nx * ny)], -1) + np.asarray(travel["origin"], np.int64)
+    return (v.astype(np.float32) * np.float32(voxel)).astype(np.float32)

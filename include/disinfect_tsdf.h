@@ -664,6 +664,70 @@ typedef struct tsdf_edt_out {
 void tsdf_edt_config_default(tsdf_edt_config* cfg);
 int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_edt_out* out);
 
+/* ---- Travel field over the box of a distance field: reachability and paths (no reference counterpart) ----
+ * The least travel cost from a set of seed voxels to every voxel of a box through passable voxels, and the
+ * paths back. The inputs are the d2 and state arrays tsdf_distance_field wrote (or any arrays of that
+ * shape), not the volume. All integers, so the result is exact. For a voxel v of the box:
+ *   passable(v): d2[v] >= clearance2 && (state[v] == 1 || (unknown_free && state[v] == 0));
+ *                state 2 (inside a surface) is never passable.
+ * A step goes from a passable voxel to a passable voxel among its 26 neighbours inside the box and costs
+ * 2 + |dx| + |dy| + |dz|: 3 across a face, 4 across an edge, 5 across a corner (the <3, 4, 5> chamfer), so
+ * cost / 3 is a length in voxels. There is no rule beyond the two end points of a step: a diagonal step may
+ * pass between two surface voxels that touch at a corner; clearance2 >= 4 rules that out, since every
+ * passable voxel is then two voxels or more from every surface voxel.
+ * cost[v] is the least total over all such paths from any seed that lies inside the box and is passable: 0
+ * at those seeds, TSDF_TRAVEL_UNREACHED wherever no path exists, impassable voxels included. Seeds outside
+ * the box or impassable are ignored; *seeded is the number of seeds used, duplicates counted once per
+ * entry. S == 0 or no usable seed gives a field of TSDF_TRAVEL_UNREACHED, TSDF_OK and *seeded = 0. The
+ * field is the unique least fixed point of the relaxation, so it does not depend on scheduling. *rounds is
+ * the number of relaxation rounds the call ran: implementation defined, reported for tests and
+ * measurements. The largest possible cost is 5 * 2^28, below 2^32.
+ * unknown_free = 1 is the optimistic planner: space no frame has observed is passable, observed surfaces
+ * and their clearance margin are not. The volume only holds blocks near surfaces, so the open interior of a
+ * room is state 0 and a field with unknown_free = 0 is confined to the thin observed-free shell around the
+ * surfaces. With unknown_free = 1 an unobserved gap in a wall leaks: the field passes through it.
+ * Required: e, cfg, d2, state and cost non-NULL, each dims[i] in 1 .. 2048, nx * ny * nz <= 2^28,
+ * clearance2 in 0 .. 65025, unknown_free 0 or 1, mem_kind one of the two, S >= 0 and seeds non-NULL when
+ * S > 0; anything else is TSDF_ERR_INVALID_ARG with nothing written. d2, state and cost are mem_kind memory
+ * alike (host: the call copies up and down; device: it runs on the engine stream); seeds, seeded and rounds
+ * are host memory. Either way the call has synchronised the engine stream when it returns: it reads a
+ * convergence counter once per batch of rounds. Should the rounds pass their proven bound (voxels + 2) the
+ * call returns TSDF_ERR_HIP instead of going on. The call does not touch the volume: the engine lends its
+ * stream and scratch (grown on demand, freed by tsdf_destroy), it sets no status bits, pending frames stay
+ * pending, and a shard engine (shard_count > 1) serves as well as any other.
+ *
+ * tsdf_travel_paths walks back from each target over such a field. v = target; while cost[v] != 0 take the
+ * first direction k, in the order dz slowest, then dy, then dx, each running -1, 0, 1 with (0, 0, 0)
+ * skipped, for which n = v + dir[k] lies in the box, cost[n] != TSDF_TRAVEL_UNREACHED and cost[n] + w[k] ==
+ * cost[v] (no wrap-around: the sum is taken in 64 bits), and go on from n. A field written by
+ * tsdf_travel_field always has such a neighbour; if none is found the walk ends there, len[t] is the
+ * negated number of voxels so far, and the call still returns TSDF_OK. path[t * max_len + j] is the j-th
+ * voxel of the walk as the linear index (z * ny + y) * nx + x, the target first and the seed last. len[t]
+ * is the full number of voxels, both ends included; only the first max_len are written, so len[t] > max_len
+ * (or len[t] < -max_len) tells the caller to ask again. len[t] = 0 for a target outside the box or
+ * unreached. The costs along a walk strictly decrease, so it ends on any input. Host and device cost give
+ * the same paths. Required: e, dims and cost non-NULL, dims as above, T >= 0, max_len >= 0,
+ * T * max_len <= 2^28 (the longest walk there can be, for one target), and targets, len (and path when
+ * max_len > 0) non-NULL when T > 0; anything else is TSDF_ERR_INVALID_ARG with nothing written. A device
+ * field's call stages T * max_len indices in engine scratch, which stays until tsdf_destroy. targets, path and len are host memory; the call synchronises
+ * the engine stream for a device field and does not use the GPU for a host field. */
+#define TSDF_TRAVEL_UNREACHED 0xFFFFFFFFu
+typedef struct tsdf_travel_config {
+  int32_t dims[3];      /* nx, ny, nz of the box: the distance field's */
+  int32_t clearance2;   /* 0 .. 65025 [voxels^2]: passable needs d2 >= clearance2 */
+  int32_t unknown_free; /* 0: unobserved voxels (state 0) are obstacles; 1: passable like free ones */
+} tsdf_travel_config;
+/* clearance2 0, unknown_free 0; dims zero */
+void tsdf_travel_config_default(tsdf_travel_config* cfg);
+int tsdf_travel_field(tsdf_engine* e, const tsdf_travel_config* cfg, const uint16_t* d2,
+                      const uint8_t* state /* nz * ny * nx, x fastest; mem_kind */,
+                      const int32_t* seeds /* host, S x 3 box-local x y z */, int32_t S,
+                      uint32_t* cost /* nz * ny * nx; mem_kind */, int mem_kind,
+                      int32_t* seeded /* host, may be NULL */, int32_t* rounds /* host, may be NULL */);
+int tsdf_travel_paths(tsdf_engine* e, const int32_t dims[3], const uint32_t* cost, int mem_kind /* cost */,
+                      const int32_t* targets /* host, T x 3 box-local */, int32_t T, int32_t max_len,
+                      int32_t* path /* host, T x max_len linear voxel indices */, int32_t* len /* host, T */);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
