@@ -299,24 +299,6 @@ __device__ __forceinline__ v2f div_pair(v2f a, v2f b, v2f y, bool act0, bool act
   return o;
 }
 
-// div_pair that also takes a == 0 on its fast path (the Newton expansion gives the signed zero
-// exactly); the semantic update's numerators are 0 wherever w_old == 0 and ln ht == 0.
-__device__ __forceinline__ v2f div_pair0(v2f a, v2f b, v2f y, bool act0, bool act1) {
-  const v2f e = vfma(-b, y, v2(1.0f, 1.0f));
-  const v2f y1 = vfma(e, y, y);
-  const v2f q = a * y1;
-  const v2f r = vfma(-b, q, a);
-  const v2f q1 = vfma(r, y1, q);
-  const v2f r1 = vfma(-b, q1, a);
-  v2f o = vfma(r1, y1, q1);
-  const float fa0 = fabsf(a.x), fb0 = fabsf(b.x), fa1 = fabsf(a.y), fb1 = fabsf(b.y);
-  const bool ok0 = (fa0 == 0.0f || (fa0 >= 0x1p-40f && fa0 <= 0x1p40f)) && fb0 >= 0x1p-40f && fb0 <= 0x1p40f;
-  const bool ok1 = (fa1 == 0.0f || (fa1 >= 0x1p-40f && fa1 <= 0x1p40f)) && fb1 >= 0x1p-40f && fb1 <= 0x1p40f;
-  if (__builtin_expect(act0 && !ok0, 0)) o.x = a.x / b.x;
-  if (__builtin_expect(act1 && !ok1, 0)) o.y = a.y / b.y;
-  return o;
-}
-
 // ---- logf / expf of the semantic update (voxel_tsdf.cu:196-202). CUDA's own (libdevice, <= 1 /
 // 2 ulp) cannot be reproduced here, and the reference's float chain is ill-conditioned near p = 1
 // (one ulp of p there moves a later p by up to ~1e-2), so the oracle fixes both functions as
@@ -400,7 +382,15 @@ __device__ __forceinline__ float sem_expf(float x) { return sem_expf2(v2(x, x)).
 // are sums of two non-positive terms, each 0 or of magnitude >= 4e-4 * 5.96e-8 (the smallest |ln x| of
 // a float x < 1) > 2^-40, and at most 44 * 27.03; wc lies in [4e-4, 44]; the quotients in [-27.03, 0],
 // so P and N lie in [e^-27.03, 1] (> 2^-40) and P + N <= 2. Every other voxel is recomputed with
-// sem_update_exact.
+// sem_update_exact. Checked on the GPU: sem_log_fast2 == sem_logf2 on every positive normal float and
+// sem_exp_fast2 == sem_expf2 on every float in [-104, 89], bit for bit (libtsdf_selfcheck,
+// tests/test_gpu_numerics.py); and the three gates themselves by a stream whose pixels and voxels sit
+// at, one ulp below and one ulp above each of them -- ht, lt around 2^-39, d around max_depth * 0.9999f
+// and at max_depth, p below 2^-39 and at 1 (under w_old > 0 and under w_old = 0, where the chain's
+// 0 * logf(0) is NaN), wc down to 4e-4 with w_old = 0 -- against the oracle through every update path
+// (tests/_sem_edges.py, tests/test_sem_edges_cpu.py, tests/test_gpu_sem_edges.py). The range has slack:
+// the expansions stay the IEEE divide's while every residual is a normal float, which holds well
+// below 2^-40 (checked down to 2^-61), so the constants 2^-39 and 0.9999 are not tight; p < 1 is.
 __device__ __forceinline__ bool sem_pixel_fast(float h, float l, float d, float max_depth) {
   return h >= 0x1p-39f && h <= 1.0f && l >= 0x1p-39f && l <= 1.0f && d <= max_depth * 0.9999f;
 }
@@ -430,14 +420,19 @@ __device__ __forceinline__ v2f sem_exp_fast2(v2f x) {  // x in [-104, 89]
   return v2(__builtin_amdgcn_ldexpf(s.x, (int)n.x), __builtin_amdgcn_ldexpf(s.y, (int)n.y));
 }
 // div_pair's expansion in two parts: the refined reciprocal y1 of b (shared by every numerator over
-// the same b), then RN(a / b) for |a| in {0} U [2^-40, 2^40], |b| in [2^-40, 2^40]
+// the same b), then RN(a / b) for |a| in {0} U [2^-40, 2^40], |b| in [2^-40, 2^40]. Checked against
+// a / b by libtsdf_selfcheck (tests/test_gpu_numerics.py: every such a, the signed zeros included,
+// against the divisors at the ends of the update's wc and P + N ranges, and 2^28 random pairs).
 __device__ __forceinline__ v2f div_refine(v2f b, v2f y) { return vfma(vfma(-b, y, v2(1.0f, 1.0f)), y, y); }
 __device__ __forceinline__ v2f div_expand(v2f a, v2f b, v2f y1) {
   const v2f q = a * y1;
   const v2f r = vfma(-b, q, a);
   const v2f q1 = vfma(r, y1, q);
   const v2f r1 = vfma(-b, q1, a);
-  return vfma(r1, y1, q1);
+  const v2f o = vfma(r1, y1, q1);
+  // the sign of q = a * y1, the quotient's: a no-op unless a == -0 (b > 0), where the residual -0 - (-0)
+  // is +0 and the corrections +0 + -0 gave +0 for the IEEE divide's -0
+  return v2(__builtin_copysignf(o.x, q.x), __builtin_copysignf(o.y, q.y));
 }
 // the whole update with every special case (IEEE divides, sem_logf / sem_expf)
 __device__ __forceinline__ float sem_update_exact(float p, float w_old, float w_new, float wc, float lnh,

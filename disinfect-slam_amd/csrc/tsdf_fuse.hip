@@ -181,7 +181,11 @@ __device__ __forceinline__ void integrate_tail(const EngineDev& D, const FramePa
 
 // One visible block's update (tsdf_integrate_kernel, voxel_tsdf.cu:149-205) by one wave of the two
 // that share it (hf: which half of its 512 voxels; 4 voxels per lane). mn: the minimum |tsdf| of the
-// lane's voxels after the update (the carving test), my_upd: + the lane's updated voxels.
+// lane's voxels after the update (the carving test), my_upd: + the lane's updated voxels. The callers
+// start mn at NaN, not +inf: every combining step is fminf, which drops a NaN operand, so the block's
+// minimum is NaN exactly when every voxel's tsdf is NaN (d == max_depth gives wc = 0 and 0 / 0), and
+// NaN >= 0.9 is false -- space_carving_kernel's own fminf reduction (voxel_tsdf.cu:218-227) keeps such a
+// block; from +inf it was carved (tests/test_gpu_sem_edges.py holds such blocks).
 // The block's loads (pool state: update_issue_pool; projection + pixel gathers: update_issue_pix) and
 // the update itself (update_finish); update_block = all three. (Issuing the next record's loads before
 // finishing this one -- all of them, or the pool state only -- measured 5-17 % slower at 4-6 waves per
@@ -535,7 +539,7 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
   // trip is not amortised.)
   for (int pp = p_lo + (blockIdx.x >> 3); pp < p_hi; pp += ngrp) {
     const int b = 2 * pp + pair;
-    float mn = __builtin_inff();
+    float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
     VisRec r{};
     if (b < nvis) {
       if (b >= nband) {
@@ -1203,7 +1207,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     // every wave runs its records at its own pace and one wave's memory waits overlap the others' work
     for (int k = pair; k < n; k += 2) {
       const VisRec r = s_list[k];
-      float mn = __builtin_inff();
+      float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
       update_block<false>(D, P, r, lane, hf, mn, my_upd);
       my_vis += hf == 0 ? 1 : 0;
       mn = wave_min_u(mn);

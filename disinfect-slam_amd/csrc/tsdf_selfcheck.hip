@@ -3,7 +3,11 @@
 // f2i / f2u8 / round_s16) bit-for-bit against the
 // correctly rounded IEEE divide and the saturating conversions, on the GPU, over exhaustive and
 // adversarial input sets; and digests the semantic update's sem_logf / sem_expf over every input for
-// comparison with the oracle's (ora_math_digest). Not part of the product library; tests/test_gpu_numerics.py drives it.
+// comparison with the oracle's (ora_math_digest). The functions the update's hot path actually calls
+// are checked against those: sem_log_fast2 == sem_logf2 on every positive normal float, sem_exp_fast2
+// == sem_expf2 on every float in [-104, 89], and div_expand over div_refine == the IEEE divide over
+// their whole range {0} U [2^-40, 2^40] against the divisors at the ends of the update's ranges.
+// Not part of the product library; tests/test_gpu_numerics.py drives it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -102,6 +106,54 @@ __global__ void k_div_pair(float b, uint32_t lo, uint32_t hi, uint32_t seed, uin
     if (!same_bits(q.x, a / bb) || !same_bits(q.y, -a / bb)) {
       atomicAdd(bad, 1ull);
       atomicMin(first, sweep ? lo + (uint32_t)i : (uint32_t)i);
+    }
+  }
+}
+
+// the semantic update's quotient, as update_finish forms it: div_expand(a, b, div_refine(b, v_rcp(b)))
+// == a / b on the pair (a, -a) (signed zeros compared by sign): every a with bits in [lo, hi) against a
+// fixed divisor b, or (lo == hi) n random pairs with |a| (random sign) and b log-uniform in
+// [2^-40, 2^40], the helpers' whole range (they have no fallback outside it)
+__global__ void k_div_expand(float b, uint32_t lo, uint32_t hi, uint32_t seed, uint64_t n,
+                             unsigned long long* bad, uint32_t* first) {
+  const bool sweep = hi > lo;
+  const uint64_t cnt = sweep ? (uint64_t)hi - lo : n;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cnt;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    float a, bb = b;
+    if (sweep) {
+      a = __uint_as_float(lo + (uint32_t)i);
+    } else {
+      const uint32_t h0 = pcg((uint32_t)i ^ seed), h1 = pcg(h0 + 0x9e3779b9u);
+      bb = __builtin_amdgcn_fmed3f(exp2f(-40.0f + 80.0f * ((h0 >> 8) * 0x1p-24f)), 0x1p-40f, 0x1p40f);
+      a = __builtin_amdgcn_fmed3f(exp2f(-40.0f + 80.0f * ((h1 >> 8) * 0x1p-24f)), 0x1p-40f, 0x1p40f);
+      if (h1 & 1u) a = -a;
+    }
+    const float y = __builtin_amdgcn_rcpf(bb);
+    const v2f b2 = v2(bb, bb);
+    const v2f q = div_expand(v2(a, -a), b2, div_refine(b2, v2(y, y)));
+    if (!same_bits(q.x, a / bb) || !same_bits(q.y, -a / bb)) {
+      atomicAdd(bad, 1ull);
+      atomicMin(first, sweep ? lo + (uint32_t)i : (uint32_t)i);
+    }
+  }
+}
+
+// the semantic update's fast functions against the full ones (which the digests below pin to the
+// oracle) on the input bit patterns [lo, hi), two consecutive inputs per pair. kind 0: sem_log_fast2
+// == sem_logf2 (meant for positive normal floats), 1: sem_exp_fast2 == sem_expf2 (for [-104, 89])
+__global__ void k_sem_fast(int kind, uint32_t lo, uint32_t hi, unsigned long long* bad, uint32_t* first) {
+  const uint64_t n = (uint64_t)hi - lo;
+  for (uint64_t i = 2 * (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x); i < n;
+       i += 2 * (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t b0 = lo + (uint32_t)i, b1 = i + 1 < n ? b0 + 1 : b0;
+    const v2f x = v2(__uint_as_float(b0), __uint_as_float(b1));
+    const v2f f = kind == 0 ? sem_log_fast2(x) : sem_exp_fast2(x);
+    const v2f e = kind == 0 ? sem_logf2(x) : sem_expf2(x);
+    const bool ok0 = same_bits(f.x, e.x), ok1 = same_bits(f.y, e.y);
+    if (!ok0 || !ok1) {
+      atomicAdd(bad, (unsigned long long)!ok0 + (b1 != b0 && !ok1));
+      atomicMin(first, ok0 ? b1 : b0);
     }
   }
 }
@@ -246,6 +298,24 @@ int tsdf_selfcheck_div_pair(float b, uint32_t lo, uint32_t hi, uint32_t seed, ui
   if (!d) return -1;
   hipLaunchKernelGGL(k_div_pair, dim3(8192), dim3(256), 0, 0, b, lo, hi, seed, n, bmin, bmax,
                      &d->bad, &d->first);
+  return finish(d, bad, first);
+}
+
+// div_expand over div_refine == IEEE a / b: sweep (lo < hi, fixed b) or random (lo == hi, n pairs)
+int tsdf_selfcheck_div_expand(float b, uint32_t lo, uint32_t hi, uint32_t seed, uint64_t n,
+                              unsigned long long* bad, uint32_t* first) {
+  Out* d = start();
+  if (!d) return -1;
+  hipLaunchKernelGGL(k_div_expand, dim3(8192), dim3(256), 0, 0, b, lo, hi, seed, n, &d->bad, &d->first);
+  return finish(d, bad, first);
+}
+
+// sem_log_fast2 (kind 0) / sem_exp_fast2 (kind 1) == sem_logf2 / sem_expf2 on the bit patterns [lo, hi)
+int tsdf_selfcheck_sem_fast(int kind, uint32_t lo, uint32_t hi, unsigned long long* bad, uint32_t* first) {
+  if (kind != 0 && kind != 1) return -1;
+  Out* d = start();
+  if (!d) return -1;
+  hipLaunchKernelGGL(k_sem_fast, dim3(8192), dim3(256), 0, 0, kind, lo, hi, &d->bad, &d->first);
   return finish(d, bad, first);
 }
 

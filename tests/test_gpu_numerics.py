@@ -17,6 +17,14 @@ Each must agree bit for bit with the correctly rounded divide / cvt.rzi semantic
 And the semantic update's sem_logf / sem_expf (and the update's unit-interval logf form) must return
 the oracle's bits (oracle/ora_math.c) for EVERY float input: digests of all 2^32 results per function,
 in chunks of 2^24, against the committed oracle digests (tests/golden/sem_math_digests.json).
+The voxel update's hot path (update_finish, pass 3) calls other forms, with no special-value handling
+and no IEEE fallback, exact only on a range; they are compared on the device with the forms above:
+ - sem_log_fast2 == sem_logf2 on every positive normal float (its domain; the update's p and 1 - p
+   are a subset), sem_exp_fast2 == sem_expf2 on every float in [-104, 89] (+-0, subnormals included);
+ - div_expand(a, b, div_refine(b, rcp(b))) == a / b for every a of both signs in [2^-40, 2^40] and
+   a = +-0 (signed), against test_div_pair_sweep's divisors, 2^-40, 2^40, 2 and the float below it
+   (P + N at its top), 2 * 2^-39 (its floor) and the smallest wc the pixel gate admits at max_depth
+   4, 1.3 and 3; and on 2^28 random pairs, both log-uniform over [2^-40, 2^40].
 """
 import ctypes as C
 import os
@@ -45,6 +53,8 @@ def lib():
     L.tsdf_selfcheck_quot_cmp.argtypes = [u32, u64, f, f, f, P64, P32]
     L.tsdf_selfcheck_div_pair.argtypes = [f, u32, u32, u32, u64, f, f, P64, P32]
     L.tsdf_selfcheck_sem_digest.argtypes = [C.c_int, u64, u64, P64]
+    L.tsdf_selfcheck_div_expand.argtypes = [f, u32, u32, u32, u64, P64, P32]
+    L.tsdf_selfcheck_sem_fast.argtypes = [C.c_int, u32, u32, P64, P32]
     return L
 
 
@@ -111,6 +121,66 @@ def test_div_pair_sweep(lib, b):
 def test_div_pair_random(lib, bmin, bmax):
     bad, first = _run(lib.tsdf_selfcheck_div_pair, 0.0, 0, 0, 4242, 1 << 28, bmin, bmax)
     assert bad == 0, f"{bad} mismatches, first sample {first}"
+
+
+def _smallest_wc(max_depth):
+    """The smallest wc sem_pixel_fast admits (w_old = 0, d = T = RN(max_depth * 0.9999f)), in float:
+    (1 - RN(T / max_depth)) * 4, pixel_w_new's operations."""
+    import numpy as np
+    one, m = np.float32(1.0), np.float32(max_depth)
+    t = np.float32(m * np.float32(0.9999))
+    return float(np.float32((one - np.float32(t / m)) * np.float32(4.0)))
+
+
+# |a| in [2^-40, 2^40], both ends included, both signs; and a = +0 / -0 (first lane: the pair is (a, -a))
+EXPAND_RANGES = [(0x2B800000, 0x53800001), (0xAB800000, 0xD3800001), (0x00000000, 0x00000001),
+                 (0x80000000, 0x80000001)]
+EXPAND_DIVISORS = [4.0, 1.0, 3.9999998, 40.5, 44.0, 7.3125, 0.0137, 2.3841858e-7, 1.5e-12,  # test_div_pair_sweep's
+                   2.0 ** -40, 2.0 ** 40,            # the ends of the helpers' range
+                   2.0, 2.0 - 2.0 ** -23,            # P + N at its upper end (P = N = 1) and just below
+                   2.0 * 2.0 ** -39,                 # the P + N floor the range argument grants (ht = lt = 2^-39)
+                   _smallest_wc(4.0), _smallest_wc(1.3), _smallest_wc(3.0)]
+
+
+@pytest.mark.parametrize("b", EXPAND_DIVISORS)
+def test_div_expand_sweep(lib, b):
+    """The semantic update's quotients (update_finish: div_expand over div_refine of v_rcp) == a / b for
+    every numerator of their range, zero with its sign included."""
+    assert 2.0 ** -40 <= C.c_float(b).value <= 2.0 ** 40
+    for lo, hi in EXPAND_RANGES:
+        bad, first = _run(lib.tsdf_selfcheck_div_expand, b, lo, hi, 0, 0)
+        assert bad == 0, f"b={b!r}: {bad} mismatches, first a bits {first:#x}"
+
+
+@pytest.mark.parametrize("seed", [4242])
+def test_div_expand_random(lib, seed):
+    bad, first = _run(lib.tsdf_selfcheck_div_expand, 0.0, 0, 0, seed, 1 << 28)
+    assert bad == 0, f"{bad} mismatches, first sample {first}"
+
+
+@pytest.mark.parametrize("lo,hi", [(0x00800000, 0x7F800000)])
+def test_sem_log_fast_equals_sem_logf(lib, lo, hi):
+    """sem_log_fast2 (the update's logf of p and 1 - p) returns sem_logf2's bits on every positive
+    normal float, its stated domain; sem_logf2 is pinned to the oracle below."""
+    bad, first = _run(lib.tsdf_selfcheck_sem_fast, 0, lo, hi)
+    assert bad == 0, f"{bad} mismatches, first x bits {first:#x}"
+
+
+@pytest.mark.parametrize("lo,hi", [(0x00000000, 0x42B20001), (0x80000000, 0xC2D00001)])
+def test_sem_exp_fast_equals_sem_expf(lib, lo, hi):
+    """sem_exp_fast2 returns sem_expf2's bits on every float in [0, 89] and [-104, -0], +-0 and the
+    subnormals included."""
+    bad, first = _run(lib.tsdf_selfcheck_sem_fast, 1, lo, hi)
+    assert bad == 0, f"{bad} mismatches, first x bits {first:#x}"
+
+
+def test_sem_fast_check_sees_a_difference_outside_the_domain(lib):
+    """The comparison is not vacuous: outside their domains the fast forms do differ from the full
+    ones (subnormal inputs of the logarithm, which the full form rescales; exp(+inf), inf - inf)."""
+    bad, first = _run(lib.tsdf_selfcheck_sem_fast, 0, 0x00000001, 0x00800000)
+    assert bad > 0 and 0x00000001 <= first < 0x00800000, (bad, hex(first))
+    bad, first = _run(lib.tsdf_selfcheck_sem_fast, 1, 0x7F800000, 0x7F800001)
+    assert (bad, first) == (1, 0x7F800000), (bad, hex(first))
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2])
