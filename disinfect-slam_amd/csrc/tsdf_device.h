@@ -605,19 +605,26 @@ __device__ __forceinline__ bool block_visible(const FrameParams& P, int16_t bx, 
 }
 
 // pixel -> normalised camera ray K^-1 [x, y, 1] (camera.cuh:47-51 with intrinsics_inv)
-__device__ __forceinline__ f3 pixel_ray(const FrameParams& P, int x, int y) {
+// (the inverse intrinsics as values: the update's Raw form holds them as loop constants)
+__device__ __forceinline__ f3 pixel_ray(float ifx, float ify, float icx, float icy, int x, int y) {
   f3 pc;
-  pc.x = P.ifx * (float)x + P.icx * 1.0f;
-  pc.y = P.ify * (float)y + P.icy * 1.0f;
+  pc.x = ifx * (float)x + icx * 1.0f;
+  pc.y = ify * (float)y + icy * 1.0f;
   pc.z = 1.0f;
   return pc;
+}
+__device__ __forceinline__ f3 pixel_ray(const FrameParams& P, int x, int y) {
+  return pixel_ray(P.ifx, P.ify, P.icx, P.icy, x, y);
 }
 // the per-pixel terms of tsdf_integrate_kernel's update (voxel_tsdf.cu:174-201), computed once per
 // pixel into the pixel records (one volume) or per voxel from the raw frame (a shard): the same
 // operations either way, so the results are identical
 //   w_new = (1 - d / max_depth) * 4
+__device__ __forceinline__ float pixel_w_new(float max_depth, float inv_max_depth, float d) {
+  return (1.0f - quot_const(d, max_depth, inv_max_depth)) * 4.0f;
+}
 __device__ __forceinline__ float pixel_w_new(const FrameParams& P, float d) {
-  return (1.0f - quot_const(d, P.max_depth, P.inv_max_depth)) * 4.0f;
+  return pixel_w_new(P.max_depth, P.inv_max_depth, d);
 }
 //   logf(ht), logf(lt) (sem_logf)
 

@@ -125,8 +125,8 @@ __global__ __launch_bounds__(256) void k_shard_abort(EngineDev D) {
 // The C5 loop's raycast view grid built inside the update launch (k_integrate_vg): the render camera,
 // its grid and the launch's release tag (the carving tags the pool blocks it releases with it)
 struct ViewFuse {
-  FrameParams R;
-  ViewGrid V;
+  const FrameParams& R;  // (in the kernel's arguments or the graph's FrameArgs block: read where used)
+  const ViewGrid& V;
   uint32_t vtag;
 };
 // the grid's cells of the blocks this launch's carving released read as missing again: the grid
@@ -152,13 +152,14 @@ __device__ __forceinline__ void view_patch_carved(const EngineDev& D, const View
     __hip_atomic_store(&V.cell[view_cell(kb, lx, ly, lz)], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-__device__ __forceinline__ void integrate_tail(const EngineDev& D, const FrameParams& P, DeleteLds& L,
+// (tail, slot, slot_cap: FrameParams' fields, or the graph frame's own)
+__device__ __forceinline__ void integrate_tail(const EngineDev& D, int tail, ShardRec* slot, int slot_cap, DeleteLds& L,
                                                const ViewFuse* F = nullptr) {
   const int t = threadIdx.x;
   const unsigned long long tend = __builtin_amdgcn_s_memrealtime();  // the update's span ends here
   TSDF_STAMP(D, 7, 0);
-  if (P.tail == kTailPack)
-    pack_cands_wg(D, D.cand, D.ncand, P.slot, P.slot_cap);
+  if (tail == kTailPack)
+    pack_cands_wg(D, D.cand, D.ncand, slot, slot_cap);
   else
     resolve_delete_wg(D, D.cand, D.ncand, 0, L, F ? F->vtag : 0u);
 #ifndef TSDF_NO_VIEW_PATCH  // (a test build leaves the released blocks' cells: the C5 tests must fail)
@@ -175,7 +176,7 @@ __device__ __forceinline__ void integrate_tail(const EngineDev& D, const FramePa
     D.ctr->integrate_ticks += tend - ld_co(&D.arrive[kArrStart]);
     D.ctr->n_vis = nband + D.ctr->n_fresh;
   }
-  if (P.tail != kTailPack) frame_end(D);
+  if (tail != kTailPack) frame_end(D);
   TSDF_STAMP(D, 7, 2);
 }
 
@@ -197,15 +198,81 @@ struct UpdState {
   float4 px[4];
   uint32_t pc[4];
   v2f hzs[2];
-  bool inb[4];
+  int inb;  // bit j: voxel j projects into the image
   bool fresh;
 };
 
-__device__ __forceinline__ void update_issue_pool(const EngineDev& D, const VisRec& r, int lane, int hf,
+// What the three parts below read from the kernel's arguments: wave-uniform values, collected once
+// before a record loop (upd_const) and passed down in place of EngineDev / FrameParams, so the loop body
+// holds no scalar load of a kernel argument. Each value goes through uniform_reg: the register allocator
+// can then keep or spill it, but not re-load it from the argument segment inside the loop (a scalar
+// memory round trip per record, waited for in the middle of pass 2).
+struct UpdConst {
+  uint8_t* pool;
+  const float4* pixA;  // this frame's pixel records (pix_off folded in); the packed form
+  const uint32_t* pixC;
+  const float* depth;  // the raw frame and its inverse intrinsics; the Raw form
+  const uint8_t* rgb;
+  const float* ht;
+  const float* lt;
+  float ifx, ify, icx, icy;
+  int W, H;
+  float voxel;
+  quatf cq;
+  f3 ct;
+  float fx, fy, cx, cy;
+  float trunc, neg_trunc, inv_trunc, max_depth, inv_max_depth;
+};
+template <typename T>
+__device__ __forceinline__ T uniform_reg(T v) {
+  asm("" : "+s"(v));
+  return v;
+}
+template <typename T>  // (a pointer stays a global one: through the asm as a generic pointer its loads became flat_load)
+__device__ __forceinline__ T* uniform_reg(T* p) {
+  auto g = (__attribute__((address_space(1))) T*)p;
+  asm("" : "+s"(g));
+  return (T*)g;
+}
+template <bool Raw>
+__device__ __forceinline__ UpdConst upd_const(const EngineDev& D, const FrameParams& P) {
+  UpdConst C{};
+  C.pool = uniform_reg(D.pool);
+  if (Raw) {
+    C.depth = uniform_reg(P.depth);
+    C.rgb = uniform_reg(P.rgb);
+    C.ht = uniform_reg(P.ht);
+    C.lt = uniform_reg(P.lt);
+    C.ifx = uniform_reg(P.ifx);
+    C.ify = uniform_reg(P.ify);
+    C.icx = uniform_reg(P.icx);
+    C.icy = uniform_reg(P.icy);
+  } else {
+    C.pixA = uniform_reg(D.pixA + P.pix_off);
+    C.pixC = uniform_reg(D.pixC + P.pix_off);
+  }
+  C.W = uniform_reg(P.W);
+  C.H = uniform_reg(P.H);
+  C.voxel = uniform_reg(P.voxel);
+  C.cq = {uniform_reg(P.cq.x), uniform_reg(P.cq.y), uniform_reg(P.cq.z), uniform_reg(P.cq.w)};
+  C.ct = {uniform_reg(P.ct.x), uniform_reg(P.ct.y), uniform_reg(P.ct.z)};
+  C.fx = uniform_reg(P.fx);
+  C.fy = uniform_reg(P.fy);
+  C.cx = uniform_reg(P.cx);
+  C.cy = uniform_reg(P.cy);
+  C.trunc = uniform_reg(P.trunc);
+  C.neg_trunc = -C.trunc;  // (a source modifier where it is compared: no register of its own)
+  C.inv_trunc = uniform_reg(P.inv_trunc);
+  C.max_depth = uniform_reg(P.max_depth);
+  C.inv_max_depth = uniform_reg(P.inv_max_depth);
+  return C;
+}
+
+__device__ __forceinline__ void update_issue_pool(const UpdConst& C, const VisRec& r, int lane, int hf,
                                                   UpdState& S) {
   const int off = (hf * 256 + lane * 4) * 4;
   const int32_t pidx = r.idx;
-  uint8_t* blk = D.pool + (size_t)pidx * kBlockBytes;
+  uint8_t* blk = C.pool + (size_t)pidx * kBlockBytes;
   float4& ts = S.ts;
   float4& pr = S.pr;
   uint4& cw = S.cw;
@@ -225,29 +292,28 @@ __device__ __forceinline__ void update_issue_pool(const EngineDev& D, const VisR
   S.fresh = fresh;
 }
 template <bool Raw>
-__device__ __forceinline__ void update_issue_pix(const EngineDev& D, const FrameParams& P, const VisRec& r, int lane,
-                                                 int hf, UpdState& S) {
+__device__ __forceinline__ void update_issue_pix(const UpdConst& C, const VisRec& r, int lane, int hf, UpdState& S) {
   const int rx0 = (lane & 1) * 4, ry = (lane >> 1) & 7, rz = (lane >> 4) + 4 * hf;
   float4* px = S.px;
   uint32_t* pc = S.pc;
   v2f* hzs = S.hzs;
-  bool* inb = S.inb;
+  int inb = 0;
   const int16_t ax0 = (int16_t)(r.x << kBlockLenBits), ay = (int16_t)((r.y << kBlockLenBits) + ry),
                 az = (int16_t)((r.z << kBlockLenBits) + rz);
-  const float fy = (float)ay * P.voxel, fz = (float)az * P.voxel;
+  const float fy = (float)ay * C.voxel, fz = (float)az * C.voxel;
   // ---- pass 1: project the lane's 4 voxels (two packed pairs) and issue every pixel gather
   // before any is consumed (predicated, so all 8 stay in flight together).
   // cam_T_world * (x voxel, fy, fz) in QuaternionBase::_transformVector's exact order, with the
   // parts that do not depend on x computed once per lane (identical operations, so identical
   // results to se3_apply per voxel).
-  const float qx = P.cq.x, qy = P.cq.y, qz = P.cq.z, qw = P.cq.w;
+  const float qx = C.cq.x, qy = C.cq.y, qz = C.cq.z, qw = C.cq.w;
   const float qx_fz = qx * fz, qx_fy = qx * fy;
   float uvx = qy * fz - qz * fy;
   uvx += uvx;
   const float w_uvx = qw * uvx, qz_uvx = qz * uvx, qy_uvx = qy * uvx;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const v2f wx = v2((float)(int16_t)(ax0 + rx0 + 2 * k), (float)(int16_t)(ax0 + rx0 + 2 * k + 1)) * P.voxel;
+    const v2f wx = v2((float)(int16_t)(ax0 + rx0 + 2 * k), (float)(int16_t)(ax0 + rx0 + 2 * k + 1)) * C.voxel;
     v2f uvy = qz * wx - qx_fz;
     v2f uvz = qx_fy - qy * wx;
     uvy += uvy;
@@ -255,11 +321,11 @@ __device__ __forceinline__ void update_issue_pix(const EngineDev& D, const Frame
     const v2f cx = qy * uvz - qz * uvy;
     const v2f cy = qz_uvx - qx * uvz;
     const v2f cz = qx * uvy - qy_uvx;
-    const v2f pcx = ((wx + w_uvx) + cx) + P.ct.x;
-    const v2f pcy = ((fy + qw * uvy) + cy) + P.ct.y;
-    const v2f pcz = ((fz + qw * uvz) + cz) + P.ct.z;
-    const v2f hx = P.fx * pcx + P.cx * pcz;
-    const v2f hy = P.fy * pcy + P.cy * pcz;
+    const v2f pcx = ((wx + w_uvx) + cx) + C.ct.x;
+    const v2f pcy = ((fy + qw * uvy) + cy) + C.ct.y;
+    const v2f pcz = ((fz + qw * uvz) + cz) + C.ct.z;
+    const v2f hx = C.fx * pcx + C.cx * pcz;
+    const v2f hy = C.fy * pcy + C.cy * pcz;
     const v2f rz = v2(__builtin_amdgcn_rcpf(pcz.x), __builtin_amdgcn_rcpf(pcz.y));
     int u0, u1, v0, v1;
     round_quot_i2(hx, pcz, rz, true, true, u0, u1);
@@ -269,42 +335,43 @@ __device__ __forceinline__ void update_issue_pix(const EngineDev& D, const Frame
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int j = 2 * k + e;
-      inb[j] = uu[e] >= 0 && uu[e] < P.W && vv[e] >= 0 && vv[e] < P.H;
+      const bool in = uu[e] >= 0 && uu[e] < C.W && vv[e] >= 0 && vv[e] < C.H;
+      inb |= in ? 1 << j : 0;
       // unconditional gathers at a clamped index (pixel 0 when out of the image): no exec-
       // masked region around the loads, so all 8 stay in flight until pass 2
-      const int img = inb[j] ? vv[e] * P.W + uu[e] : 0;
+      const int img = in ? vv[e] * C.W + uu[e] : 0;
       if (Raw) {  // x: depth, y / z: ht / lt (their logs, range and w_new computed in pass 2)
-        pc[j] = (uint32_t)P.rgb[3 * img] | ((uint32_t)P.rgb[3 * img + 1] << 8) |
-                ((uint32_t)P.rgb[3 * img + 2] << 16);
-        px[j] = make_float4(P.depth[img], P.ht ? P.ht[img] : 1.0f, P.lt ? P.lt[img] : 1.0f,
+        pc[j] = (uint32_t)C.rgb[3 * img] | ((uint32_t)C.rgb[3 * img + 1] << 8) |
+                ((uint32_t)C.rgb[3 * img + 2] << 16);
+        px[j] = make_float4(C.depth[img], C.ht ? C.ht[img] : 1.0f, C.lt ? C.lt[img] : 1.0f,
                             __int_as_float((uu[e] & 0xFFFF) | (vv[e] << 16)));  // w: the pixel (u, v)
       } else {  // x: depth, y: range, z: logf(ht), w: logf(lt) (w_new computed in pass 2)
-        px[j] = D.pixA[P.pix_off + img];
-        pc[j] = D.pixC[P.pix_off + img];
+        px[j] = C.pixA[img];
+        pc[j] = C.pixC[img];
       }
     }
   }
+  S.inb = inb;
 }
 
 template <bool Raw>
-__device__ __forceinline__ void update_issue(const EngineDev& D, const FrameParams& P, const VisRec& r, int lane,
-                                             int hf, UpdState& S) {
-  update_issue_pool(D, r, lane, hf, S);
-  update_issue_pix<Raw>(D, P, r, lane, hf, S);
+__device__ __forceinline__ void update_issue(const UpdConst& C, const VisRec& r, int lane, int hf, UpdState& S) {
+  update_issue_pool(C, r, lane, hf, S);
+  update_issue_pix<Raw>(C, r, lane, hf, S);
 }
 
 template <bool Raw>
-__device__ __forceinline__ void update_finish(const EngineDev& D, const FrameParams& P, const VisRec& r, int lane,
-                                              int hf, UpdState& S, float& mn, int& my_upd) {
+__device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r, int lane, int hf, UpdState& S,
+                                              float& mn, int& my_upd) {
   const int off = (hf * 256 + lane * 4) * 4;
-  const float neg_trunc = -P.trunc;
-  uint8_t* blk = D.pool + (size_t)r.idx * kBlockBytes;
+  const float neg_trunc = C.neg_trunc;
+  uint8_t* blk = C.pool + (size_t)r.idx * kBlockBytes;
   float4 ts = S.ts, pr = S.pr;
   uint4 cw = S.cw;
   const float4* px = S.px;
   const uint32_t* pc = S.pc;
   const v2f* hzs = S.hzs;
-  const bool* inb = S.inb;
+  const int inb = S.inb;
   const bool fresh = S.fresh;
   int upd_mask = 0;
   // ---- pass 2: tsdf_integrate_kernel's update (voxel_tsdf.cu:174-203) of tsdf, colour and weight,
@@ -325,14 +392,14 @@ __device__ __forceinline__ void update_finish(const EngineDev& D, const FramePar
     bool pf0, pf1;  // sem_pixel_fast
     if (Raw) {  // the ingest's per-pixel terms (identical operations)
       const int w0 = __float_as_int(px[j0].w), w1 = __float_as_int(px[j1].w);
-      const f3 r0 = pixel_ray(P, w0 & 0xFFFF, w0 >> 16);
-      const f3 r1 = pixel_ray(P, w1 & 0xFFFF, w1 >> 16);
+      const f3 r0 = pixel_ray(C.ifx, C.ify, C.icx, C.icy, w0 & 0xFFFF, w0 >> 16);
+      const f3 r1 = pixel_ray(C.ifx, C.ify, C.icx, C.icy, w1 & 0xFFFF, w1 >> 16);
       rng = v2(sqrtf(dot3(r0, r0)), sqrtf(dot3(r1, r1)));
-      w_new = v2(pixel_w_new(P, d.x), pixel_w_new(P, d.y));
+      w_new = v2(pixel_w_new(C.max_depth, C.inv_max_depth, d.x), pixel_w_new(C.max_depth, C.inv_max_depth, d.y));
       lnh = sem_logf2(v2(px[j0].y, px[j1].y));
       lnl = sem_logf2(v2(px[j0].z, px[j1].z));
-      pf0 = sem_pixel_fast(px[j0].y, px[j0].z, d.x, P.max_depth);
-      pf1 = sem_pixel_fast(px[j1].y, px[j1].z, d.y, P.max_depth);
+      pf0 = sem_pixel_fast(px[j0].y, px[j0].z, d.x, C.max_depth);
+      pf1 = sem_pixel_fast(px[j1].y, px[j1].z, d.y, C.max_depth);
     } else {
       rng = v2(fabsf(px[j0].y), fabsf(px[j1].y));
       pf0 = px[j0].y > 0.0f;
@@ -342,13 +409,13 @@ __device__ __forceinline__ void update_finish(const EngineDev& D, const FramePar
     }
     const uint32_t n0 = pc[j0], n1 = pc[j1];
     const v2f sdf = rng * (d - hzs[k]);
-    const bool a0 = inb[j0] && !(d.x == 0 || d.x > P.max_depth) && sdf.x > neg_trunc;
-    const bool a1 = inb[j1] && !(d.y == 0 || d.y > P.max_depth) && sdf.y > neg_trunc;
+    const bool a0 = ((inb >> j0) & 1) && !(d.x == 0 || d.x > C.max_depth) && sdf.x > neg_trunc;
+    const bool a1 = ((inb >> j1) & 1) && !(d.y == 0 || d.y > C.max_depth) && sdf.y > neg_trunc;
     if (a0 || a1) {
       // w_new = (1 - d / max_depth) * 4 (pixel_w_new's operations, on the pair; the 16-B pixel record
       // has no room for it: one gather per voxel instead of two)
-      if (!Raw) w_new = (v2(1.0f, 1.0f) - quot_const2(d, P.max_depth, P.inv_max_depth, a0, a1)) * v2(4.0f, 4.0f);
-      v2f tn = quot_const2(sdf, P.trunc, P.inv_trunc, a0, a1);
+      if (!Raw) w_new = (v2(1.0f, 1.0f) - quot_const2(d, C.max_depth, C.inv_max_depth, a0, a1)) * v2(4.0f, 4.0f);
+      v2f tn = quot_const2(sdf, C.trunc, C.inv_trunc, a0, a1);
       tn = v2(fminf(1.0f, tn.x), fminf(1.0f, tn.y));
       const uint32_t o0 = compu(cw, j0), o1 = compu(cw, j1);
       const v2f w_old = v2((float)(o0 >> 24), (float)(o1 >> 24));
@@ -445,11 +512,11 @@ __device__ __forceinline__ void update_finish(const EngineDev& D, const FramePar
 }
 
 template <bool Raw>
-__device__ __forceinline__ void update_block(const EngineDev& D, const FrameParams& P, const VisRec& r, int lane,
-                                             int hf, float& mn, int& my_upd) {
+__device__ __forceinline__ void update_block(const UpdConst& C, const VisRec& r, int lane, int hf, float& mn,
+                                             int& my_upd) {
   UpdState S;
-  update_issue<Raw>(D, P, r, lane, hf, S);
-  update_finish<Raw>(D, P, r, lane, hf, S, mn, my_upd);
+  update_issue<Raw>(C, r, lane, hf, S);
+  update_finish<Raw>(C, r, lane, hf, S, mn, my_upd);
 }
 
 // The concatenated band lists: band i holds visible-block indices [start_i, start_i + count_i).
@@ -497,14 +564,7 @@ template <bool Graph, bool Raw>
 __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FrameParams& Pv,
                                                const FrameArgs* __restrict__ A, int nint, DeleteLds& L,
                                                int narrive = 0, const ViewFuse* F = nullptr) {
-  FrameParams P = Graph ? A->P : Pv;
-  if (Graph && A->cands_out) {  // a shard's graph frame: the tail packs the carve candidates
-    P.tail = kTailPack;
-    P.slot = A->cands_out;
-    P.slot_cap = A->cand_cap;
-  } else if (Graph) {
-    P.tail = kTailResolve;
-  }
+  const FrameParams& P = Graph ? A->P : Pv;  // (read in place: a copy is loaded whole at the kernel's entry)
   __shared__ float s_min[4];
   __shared__ int s_upd[4];
   __shared__ int s_last;
@@ -537,17 +597,25 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
   // (The chunked, barrier-free form of pipe_update measured slower here, 14.07-14.27k vs 14.8k frames/s
   // at C4 on one box: a k_integrate workgroup updates one or two pairs, so the collection's extra round
   // trip is not amortised.)
+  const UpdConst C = upd_const<Raw>(D, P);
+  // (the list walk's pointers likewise: single registers, not lanes of the argument loads' 8-register
+  // results, which a spill reload reads back whole)
+  const VisRec* vis = uniform_reg(D.vis);
+  const VisRec* fresh_vis = uniform_reg(D.fresh_vis);
+  const int nblocks = uniform_reg(D.nblocks);
+  VisRec* cand = uniform_reg(D.cand);  // (the full-buffer path of the candidates)
+  int32_t* ncand = uniform_reg(D.ncand);
   for (int pp = p_lo + (blockIdx.x >> 3); pp < p_hi; pp += ngrp) {
     const int b = 2 * pp + pair;
     float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
     VisRec r{};
     if (b < nvis) {
       if (b >= nband) {
-        r = D.fresh_vis[b - nband];
+        r = fresh_vis[b - nband];
       } else {
-        r = D.vis[band_find(D, bst, lane, b)];
+        r = vis[band_find_n(nblocks, bst, lane, b)];
       }
-      update_block<Raw>(D, P, r, lane, hf, mn, my_upd);
+      update_block<Raw>(C, r, lane, hf, mn, my_upd);
     }
     mn = wave_min_u(mn);
     if (lane == 0) s_min[wave] = mn;
@@ -559,8 +627,8 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
         if (k < kIntegrateCandBuf) {
           s_cand[k] = r;
         } else {  // buffer full (heavy carving): publish this one now
-          const int kg = atomicAdd(D.ncand, 1);
-          st_rec_co(&D.cand[kg], r);
+          const int kg = atomicAdd(ncand, 1);
+          st_rec_co(&cand[kg], r);
           s_ovf = 1;
         }
       }
@@ -598,16 +666,35 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
   const bool drain = (wave == 0 && nc > 0) || (s_ovf && (wave & 1) == 0);
   if (!arrive_last(D.arrive + kArrIntegrate, wg_upd, &s_last, drain, (uint32_t)(narrive ? narrive : nint)))
     return false;
-  integrate_tail(D, P, L, F);
+  if (Graph && A->cands_out)  // a shard's graph frame: the tail packs the carve candidates
+    integrate_tail(D, kTailPack, A->cands_out, A->cand_cap, L, F);
+  else if (Graph)
+    integrate_tail(D, kTailResolve, nullptr, 0, L, F);
+  else
+    integrate_tail(D, P.tail, P.slot, P.slot_cap, L, F);
   return true;
 }
 
+// A kernel's arguments read in place, where the code uses them. By-value struct parameters are copied at
+// the kernel's entry: every field is loaded there and stays live (in registers or spill lanes) through
+// the whole kernel. T: the parameters as they lie in the kernel-argument segment (each at its own
+// alignment from offset 0: a struct's layout).
+template <typename T>
+__device__ __forceinline__ const T& kernel_args() {
+  return *(const T*)(const __attribute__((address_space(4))) T*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+struct IntegrateKernArgs {
+  EngineDev D;
+  FrameParams Pv;
+  const FrameArgs* A;
+};
 template <bool Graph, bool Raw>
 __global__ __launch_bounds__(kIntegrateThreads)
 __attribute__((amdgpu_waves_per_eu(TSDF_INTEGRATE_WAVES, TSDF_INTEGRATE_WAVES))) void k_integrate_t(
     EngineDev D, FrameParams Pv, const FrameArgs* __restrict__ A) {
   __shared__ DeleteLds L;  // the last-arriving workgroup's carving resolve
-  integrate_body<Graph, Raw>(D, Pv, A, (int)gridDim.x, L);
+  const IntegrateKernArgs& K = kernel_args<IntegrateKernArgs>();
+  integrate_body<Graph, Raw>(K.D, K.Pv, A, (int)gridDim.x, L);
 }
 
 // k_integrate with the C5 loop's view grid (tsdf_raycast_deferred after an unpipelined update):
@@ -647,19 +734,24 @@ __device__ __forceinline__ void integrate_vg(const EngineDev& D, const FramePara
   }
   __shared__ int s_last;
   if (!arrive_last(D.arrive + kArrIntegrate, 0ull, &s_last, true, (uint32_t)narr)) return;
-  if (Graph) {  // (integrate_body's graph parameters: the frame's camera, the carving tail)
-    FrameParams P = A->P;
-    P.tail = kTailResolve;
-    integrate_tail(D, P, L, &F);
-  } else {
-    integrate_tail(D, Pv, L, &F);
-  }
+  if (Graph)  // (integrate_body's graph tail: the carving)
+    integrate_tail(D, kTailResolve, nullptr, 0, L, &F);
+  else
+    integrate_tail(D, Pv.tail, Pv.slot, Pv.slot_cap, L, &F);
 }
+struct IntegrateVgKernArgs {
+  EngineDev D;
+  FrameParams Pv, R;
+  ViewGrid V;
+  uint32_t vtag;
+  int nint;
+};
 __global__ __launch_bounds__(kIntegrateThreads)
 __attribute__((amdgpu_waves_per_eu(TSDF_INTEGRATE_WAVES, TSDF_INTEGRATE_WAVES))) void k_integrate_vg(
     EngineDev D, FrameParams Pv, FrameParams R, ViewGrid V, uint32_t vtag, int nint) {
   __shared__ DeleteLds L;
-  integrate_vg<false>(D, Pv, nullptr, R, V, vtag, nint, L);
+  const IntegrateVgKernArgs& K = kernel_args<IntegrateVgKernArgs>();
+  integrate_vg<false>(K.D, K.Pv, nullptr, K.R, K.V, vtag, nint, L);
 }
 // the graph-captured form (a render graph's update node): camera, render camera, grid and release tag
 // from the frame's argument block
@@ -667,7 +759,8 @@ __global__ __launch_bounds__(kIntegrateThreads)
 __attribute__((amdgpu_waves_per_eu(TSDF_INTEGRATE_WAVES, TSDF_INTEGRATE_WAVES))) void k_integrate_vg_g(
     EngineDev D, const FrameArgs* __restrict__ A, int nint) {
   __shared__ DeleteLds L;
-  integrate_vg<true>(D, FrameParams{}, A, A->R, A->V, A->vtag, nint, L);
+  const EngineDev& Dk = kernel_args<EngineDev>();  // (the first argument)
+  integrate_vg<true>(Dk, A->P, A, A->R, A->V, A->vtag, nint, L);
 }
 
 // =============================================================================================
@@ -1076,7 +1169,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = wave >> 1, hf = wave & 1;
   const bool t0 = threadIdx.x == 0;
-  const uint32_t fb = A.fid_alloc, fc = A.fid_carve;
+  const uint32_t fb = uniform_reg(A.fid_alloc), fc = uniform_reg(A.fid_carve);
   // frame b's view (frame_view)
   const VisRec* vis = D.vis + (size_t)(fb & 1u) * kBands * (size_t)D.nblocks;
   VisRec* cand = D.cand + (size_t)(fb & 1u) * (size_t)D.cand_cap;
@@ -1123,6 +1216,14 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   if (t0) s_fb = fb;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   if (t0) s_ndef = 0;  // (ordered before its first read by the loop's barrier)
+  const UpdConst C = upd_const<false>(D, P);
+  // (what the collection and the candidate path read from the arguments, likewise: the loop re-loads none)
+  const VisRec* fresh_vis = uniform_reg(D.fresh_vis);
+  const int nblocks = uniform_reg(D.nblocks), cand_cap = uniform_reg(D.cand_cap);
+  uint32_t* rtag = uniform_reg(D.rtag);
+  uint32_t* ctag_b = uniform_reg(D.ctag + (size_t)(fb & 1u) * D.nblocks);  // frame b's candidate tags
+  uint32_t* status = uniform_reg(&D.ctr->status);
+  const uint32_t tag = uniform_reg(A.tag);
   for (;;) {  // (all control flow below is workgroup-uniform; thread 0 writes the LDS lists)
     // ---- collect: the next records of the list walk, or (at its end) the deferred ones
     int n = 0;
@@ -1145,9 +1246,9 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
         VisRec r{};
         if (valid) {
           if (b >= nband)
-            r = fresh_co ? ld_rec_co(&D.fresh_vis[b - nband]) : D.fresh_vis[b - nband];
+            r = fresh_co ? ld_rec_co(&fresh_vis[b - nband]) : fresh_vis[b - nband];
           else
-            r = vis[(size_t)bd * D.nblocks + (size_t)(b - bs)];
+            r = vis[(size_t)bd * nblocks + (size_t)(b - bs)];
         }
         const bool cand = valid && chk && r.pad == 0 && ct[r.idx] == fc;  // a candidate of frame b - 1
         bool take = valid && !cand;
@@ -1158,9 +1259,9 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
             if (cand) s_def[ndef + __popcll(cm & lt_mask)] = r;
             ndef += nc;
           } else {
-            if (!carved_known) wave_wait_tag(carved, A.tag, &D.ctr->status);
+            if (!carved_known) wave_wait_tag(carved, tag, status);
             carved_known = true;
-            if (cand) take = lane_kept(D.rtag, r.idx, fc);
+            if (cand) take = lane_kept(rtag, r.idx, fc);
           }
         }
         const unsigned long long tm = __ballot(take);
@@ -1174,13 +1275,13 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
       p += npr * pstep;
     } else if (!def_done && s_ndef > 0) {  // (s_ndef: read before the next collection's barrier)
       if (wave == 0) {
-        if (!carved_known) wave_wait_tag(carved, A.tag, &D.ctr->status);
+        if (!carved_known) wave_wait_tag(carved, tag, status);
         carved_known = true;
         bool take = false;
         VisRec r{};
         if (lane < ndef) {
           r = s_def[lane];
-          take = lane_kept(D.rtag, r.idx, fc);
+          take = lane_kept(rtag, r.idx, fc);
         }
         const unsigned long long tm = __ballot(take);
         if (take) s_list[__popcll(tm & lt_mask)] = r;
@@ -1205,11 +1306,11 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     // ---- update: the two pairs of waves take records pair, pair + 2, ...; no workgroup barrier: the
     // two waves of a record combine their carve minima through LDS (the second to finish decides), so
     // every wave runs its records at its own pace and one wave's memory waits overlap the others' work
+    if (hf == 0 && n > pair) my_vis += (n - pair + 1) >> 1;  // (the records of this pair of waves, below)
     for (int k = pair; k < n; k += 2) {
       const VisRec r = s_list[k];
       float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
-      update_block<false>(D, P, r, lane, hf, mn, my_upd);
-      my_vis += hf == 0 ? 1 : 0;
+      update_block<false>(C, r, lane, hf, mn, my_upd);
       mn = wave_min_u(mn);
       if (lane == 0) {
         s_pmin[2 * k + hf] = mn;
@@ -1219,14 +1320,14 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
           const float m2 = fminf(mn, s_pmin[2 * k + (hf ^ 1)]);
           if (m2 >= 0.9f) {  // space_carving_kernel threshold (voxel_tsdf.cu:227, :485)
             const uint32_t f = s_fb;
-            D.ctag[(size_t)(f & 1u) * D.nblocks + r.idx] = f;  // (read by the next launch's update)
+            ctag_b[r.idx] = f;  // (read by the next launch's update)
             const int kc = atomicAdd(&s_ncand, 1);
             if (kc < kIntegrateCandBuf) {
               s_cand[kc] = r;
             } else {  // buffer full (heavy carving): this one now
               const int kg = atomicAdd(ncand, 1);
-              if (kg < D.cand_cap) st_rec_co(&cand[kg], r);
-              else atomicOr(&D.ctr->status, 16u);  // (a list longer than the pool: internal error)
+              if (kg < cand_cap) st_rec_co(&cand[kg], r);
+              else atomicOr(status, 16u);  // (a list longer than the pool: internal error)
             }
           }
         }
@@ -1358,20 +1459,26 @@ __device__ __forceinline__ void frame_body(const EngineDev& D, const FrameParams
   (void)code;
 #endif
 }
+struct FrameKernArgs {
+  EngineDev D;
+  FrameParams Pu, Pn;
+  PipeArgs A;
+};
 __global__ __launch_bounds__(kIntegrateThreads)
 __attribute__((amdgpu_waves_per_eu(TSDF_FRAME_WAVES, TSDF_FRAME_WAVES))) void k_frame(
     EngineDev D, FrameParams Pu, FrameParams Pn, PipeArgs A) {
   __shared__ FrameLds U;
-  frame_body(D, Pu, Pn, A, U);
+  const FrameKernArgs& K = kernel_args<FrameKernArgs>();  // (each part loads what it uses, in its own branch)
+  frame_body(K.D, K.Pu, K.Pn, K.A, U);
 }
 // the graph-captured form: its arguments from the FrameArgs block the graph's first node uploads
 __global__ __launch_bounds__(kIntegrateThreads)
 __attribute__((amdgpu_waves_per_eu(TSDF_FRAME_WAVES, TSDF_FRAME_WAVES))) void k_frame_g(
     EngineDev D, const FrameArgs* __restrict__ FA) {
   __shared__ FrameLds U;
-  const PipeArgs A = FA->pipe;
-  const FrameParams Pu = FA->Pu, Pn = FA->P;
-  frame_body(D, Pu, Pn, A, U);
+  // (read where a part uses them, not copied here: copies of all three stayed live across every part,
+  // ~110 scalar registers spilled and read back inside the update loop)
+  frame_body(kernel_args<EngineDev>(), FA->Pu, FA->P, FA->pipe, U);
 }
 
 template __global__ void k_integrate_t<false, false>(EngineDev, FrameParams, const FrameArgs*);
