@@ -141,6 +141,7 @@ struct TraceRange {
 // the environment's A/B and test knobs (the table of variables: read_env_knobs, tsdf_engine.hip)
 struct EnvKnobs {
   bool pipeline = true;
+  bool free_cull = true;  // (beside `pipeline`, in its padding: the struct keeps its size)
   int64_t pipe_max_pixels = -1;
   int frame_order = -1, frame_upd_wgs = 0, cand_cap = 0, mesh_grid = 0;
 };
@@ -307,6 +308,10 @@ struct tsdf_engine {
   // each; or a paths call's targets, lengths and paths. Grow-only. (Last: the frame path's fields keep
   // their offsets.)
   DevBuf<uint8_t> tv_buf;
+  // observed free space (tsdf_free_observe / tsdf_free_apply; tsdf_host_free.hip): a frame's pixel records
+  // or an apply's counter, then, for host arrays, their staging, one section each. Grow-only. (Last, as
+  // tv_buf was: the frame path's fields keep their offsets.)
+  DevBuf<uint8_t> fr_buf;
 
   tsdf_engine() = default;
   // D's buffers, the pinned mirrors, events and streams; the scratch above frees itself. The caller has

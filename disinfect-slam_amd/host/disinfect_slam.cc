@@ -77,6 +77,12 @@ TravelField DISINFSystem::query_travel_field(const DistanceField& field, const s
   return TSDF_->TravelField(field, seeds, clearance2, unknown_free);
 }
 
+void DISINFSystem::enable_free_space(const BoundingCube<float>& volumn) { TSDF_->EnableFreeSpace(volumn); }
+
+DistanceField DISINFSystem::query_free_space(const DistanceField& field, int64_t* promoted) {
+  return TSDF_->ApplyFreeSpace(field, promoted);
+}
+
 void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {
   const size_t nv = mesh.verts.size() / 3;
   if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);

@@ -71,6 +71,15 @@ class DISINFSystem {
   // tsdf().TravelPaths gives the way to a chosen stop.
   TravelField query_travel_field(const DistanceField& field, const std::vector<float>& from_world,
                                  float clearance_m = 0.0f, bool unknown_free = false);
+  // Observed free space (DESIGN.md "Observed free space"). Opt-in: once enabled, every frame integrated from
+  // then on is also observed into a layer over `volumn` that the system owns -- a bit per voxel, set when a
+  // depth frame saw the voxel as free, whether or not its block exists. query_free_space returns a copy of a
+  // distance field with its unobserved voxels promoted to free where the layer says so (*promoted: how many),
+  // to be handed to query_travel_field(..., unknown_free = false): the field then floods exactly the space the
+  // camera saw empty, and a gap in a wall nobody looked through does not leak. The camera centre itself is
+  // never marked: start from a position in front of the camera. Without enable_free_space nothing changes.
+  void enable_free_space(const BoundingCube<float>& volumn);
+  DistanceField query_free_space(const DistanceField& field, int64_t* promoted = nullptr);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

@@ -154,6 +154,29 @@ std::vector<std::vector<int32_t>> TSDFSystem::TravelPaths(const struct TravelFie
   return tsdf_.TravelPaths(travel, targets, max_len);
 }
 
+void TSDFSystem::EnableFreeSpace(const BoundingCube<float>& volumn) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  free_ = std::make_unique<FreeLayer>(tsdf_.MakeFreeLayer(volumn));
+}
+
+struct DistanceField TSDFSystem::ApplyFreeSpace(const struct DistanceField& field, int64_t* promoted) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  if (!free_) throw std::logic_error("TSDFSystem::ApplyFreeSpace: EnableFreeSpace first");
+  return tsdf_.ApplyFree(*free_, field, promoted);
+}
+
+FreeLayer TSDFSystem::FreeSpace() {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  if (!free_) throw std::logic_error("TSDFSystem::FreeSpace: EnableFreeSpace first");
+  return *free_;
+}
+
 void TSDFSystem::ImportBlocks(const void* records, int64_t n, bool replace) {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
@@ -199,6 +222,15 @@ void TSDFSystem::Run() {
       else
         tsdf_.Integrate(input->img_rgb, input->img_depth, input->img_ht, input->img_lt, max_depth_,
                         intrinsics_, input->cam_T_world);
+      if (free_) {  // the space this frame saw empty (EnableFreeSpace)
+        if (input->depth_factor > 0.0f) {
+          Mat rgb_half, depth_half;
+          tsdf_.HalfRGBD(input->img_rgb, input->img_depth, input->img_ht, input->depth_factor, &rgb_half, &depth_half);
+          tsdf_.ObserveFree(*free_, depth_half, max_depth_, intrinsics_, input->cam_T_world);
+        } else {
+          tsdf_.ObserveFree(*free_, input->img_depth, max_depth_, intrinsics_, input->cam_T_world);
+        }
+      }
     } catch (const std::exception& ex) {  // never let an engine error kill the worker
       std::fprintf(stderr, "[TSDF System] integrate failed: %s\n", ex.what());
     }

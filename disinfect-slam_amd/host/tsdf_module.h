@@ -90,6 +90,14 @@ class TSDFSystem {
   std::vector<std::vector<int32_t>> TravelPaths(const struct TravelField& travel, const std::vector<int32_t>& targets,
                                                 int max_len = 4096);
   float voxel_size() const { return tsdf_.voxel_size(); }
+  // Observed free space (TSDFGrid::ObserveFree / ApplyFree). EnableFreeSpace: from the next queued frame on,
+  // the worker also observes every frame it integrates into a layer over `volumn` that the system owns (a raw
+  // frame's half-size depth is taken from HalfRGBD once more); calling it again starts a cleared layer.
+  // ApplyFreeSpace: the field promoted by that layer, after every queued frame (std::logic_error before
+  // EnableFreeSpace). FreeSpace: a copy of the layer. Without EnableFreeSpace nothing changes.
+  void EnableFreeSpace(const BoundingCube<float>& volumn);
+  struct DistanceField ApplyFreeSpace(const struct DistanceField& field, int64_t* promoted = nullptr);
+  FreeLayer FreeSpace();
   // the volume replaced by (replace) or extended with n block records (tsdf_import_blocks, host memory;
   // one unsharded volume only), after every queued frame
   void ImportBlocks(const void* records, int64_t n, bool replace);
@@ -113,6 +121,7 @@ class TSDFSystem {
   std::queue<std::unique_ptr<TSDFSystemInput>> inputs_;
   bool busy_ = false;
   std::mutex mtx_read_;
+  std::unique_ptr<FreeLayer> free_;  // under mtx_read_; null until EnableFreeSpace
   bool terminate_ = false;
   std::thread t_;
 };

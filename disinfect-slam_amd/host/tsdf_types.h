@@ -260,6 +260,26 @@ struct TravelField {
   size_t at(int x, int y, int z) const { return ((size_t)z * dims[1] + y) * dims[0] + x; }
 };
 
+// An observed-free-space layer (tsdf_free_observe / tsdf_free_apply): a bit per voxel of a box, set when a
+// depth frame saw the voxel as free. Voxel (x, y, z) of the box is global voxel origin + (x, y, z) and bit
+// x & 31 of word (z * ny + y) * wx + (x >> 5), wx = ceil(nx / 32). Host memory: the facade carries no HIP
+// types, so an observe copies the words up and down.
+struct FreeLayer {
+  int32_t origin[3] = {0, 0, 0};
+  int32_t dims[3] = {0, 0, 0};  // nx, ny, nz
+  std::vector<uint32_t> bits;   // nz * ny * wx
+  int64_t frames = 0;           // frames observed into it
+  bool free_at(int x, int y, int z) const {
+    const size_t wx = ((size_t)dims[0] + 31) >> 5;
+    return (bits[((size_t)z * dims[1] + y) * wx + ((size_t)x >> 5)] >> (x & 31)) & 1u;
+  }
+  int64_t count() const {
+    int64_t n = 0;
+    for (uint32_t w : bits) n += __builtin_popcount(w);
+    return n;
+  }
+};
+
 // The pose of a depth frame against the volume (tsdf_track). degenerate: too few correspondences
 // or singular normal equations; pose is then the last good estimate (the guess when none was made).
 struct TrackResult {

@@ -318,6 +318,59 @@ std::vector<std::vector<int32_t>> TSDFGrid::TravelPaths(const struct TravelField
   return out;
 }
 
+FreeLayer TSDFGrid::MakeFreeLayer(const BoundingCube<float>& volumn) const {
+  const double lo[3] = {volumn.xmin, volumn.ymin, volumn.zmin}, hi[3] = {volumn.xmax, volumn.ymax, volumn.zmax};
+  FreeLayer l;
+  for (int a = 0; a < 3; ++a) {  // (DistanceField's box of the same cube)
+    const double v0 = std::ceil(lo[a] / (double)voxel_size_), v1 = std::floor(hi[a] / (double)voxel_size_);
+    if (!(v0 <= v1) || !(v0 > -1e9) || !(v1 < 1e9) || v1 - v0 >= 2048.0)
+      throw std::invalid_argument("TSDFGrid::MakeFreeLayer: the cube holds no voxel centre, or more than 2048 along an axis");
+    l.origin[a] = (int32_t)v0;
+    l.dims[a] = (int32_t)(v1 - v0) + 1;
+  }
+  const int64_t words = tsdf_free_words(l.dims);
+  if (words == 0) throw std::invalid_argument("TSDFGrid::MakeFreeLayer: more than 2^28 voxels");
+  l.bits.assign((size_t)words, 0u);
+  return l;
+}
+
+void TSDFGrid::ObserveFree(FreeLayer& layer, const Mat& img_depth, float max_depth,
+                           const CameraIntrinsics<float>& intrinsics, const SE3<float>& cam_T_world) {
+  if (group_) throw std::runtime_error("TSDFGrid::ObserveFree: not available on a sharded volume");
+  if (img_depth.type() != CV_32FC1 || img_depth.empty())
+    throw std::invalid_argument("TSDFGrid::ObserveFree: expects a CV_32FC1 depth image");
+  if ((int64_t)layer.bits.size() != tsdf_free_words(layer.dims) || layer.bits.empty())
+    throw std::invalid_argument("TSDFGrid::ObserveFree: the layer's words do not match its box");
+  tsdf_free_box box;
+  for (int a = 0; a < 3; ++a) box.origin[a] = layer.origin[a], box.dims[a] = layer.dims[a];
+  const tsdf_intrinsics K{intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy};
+  const tsdf_pose P = to_pose(cam_T_world);
+  check_tsdf(tsdf_free_observe(engine_, &box, layer.bits.data(), img_depth.ptr<float>(), img_depth.cols,
+                               img_depth.rows, TSDF_MEM_HOST, &K, &P, max_depth),
+             "tsdf_free_observe");
+  ++layer.frames;
+}
+
+struct DistanceField TSDFGrid::ApplyFree(const FreeLayer& layer, const struct DistanceField& field,
+                                         int64_t* promoted) {
+  if (group_) throw std::runtime_error("TSDFGrid::ApplyFree: not available on a sharded volume");
+  if ((int64_t)layer.bits.size() != tsdf_free_words(layer.dims) || layer.bits.empty())
+    throw std::invalid_argument("TSDFGrid::ApplyFree: the layer's words do not match its box");
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) n *= (size_t)std::max(field.dims[a], 0);
+  if (n == 0 || field.state.size() != n)
+    throw std::invalid_argument("TSDFGrid::ApplyFree: the field needs a state for every voxel of its box");
+  struct DistanceField out = field;
+  tsdf_free_box box;
+  for (int a = 0; a < 3; ++a) box.origin[a] = layer.origin[a], box.dims[a] = layer.dims[a];
+  int64_t count = 0;
+  check_tsdf(tsdf_free_apply(engine_, &box, layer.bits.data(), out.origin, out.dims, out.state.data(), TSDF_MEM_HOST,
+                             &count),
+             "tsdf_free_apply");
+  if (promoted) *promoted = count;
+  return out;
+}
+
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {
   if (group_) throw std::runtime_error("TSDFGrid::RayCastSurface: not available on a sharded volume");
   SurfaceMaps m;

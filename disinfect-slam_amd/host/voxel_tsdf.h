@@ -91,6 +91,19 @@ class TSDFGrid {
                                                 int max_len = 4096);
   float voxel_size() const { return voxel_size_; }
 
+  // Observed free space (tsdf_free_observe / tsdf_free_apply). MakeFreeLayer: a cleared layer over the voxels
+  // whose centres lie in `volumn` (the box DistanceField takes for the same cube). ObserveFree: every voxel of
+  // the layer's box that this depth frame (CV_32FC1 [m]) saw as free -- the update's own projection, sdf >=
+  // truncation, in front of the camera plane -- gets its bit set, whether or not its block exists. ApplyFree:
+  // a copy of the field with state 0 promoted to 1 where the layer's bit is set (the boxes may differ);
+  // *promoted the number of voxels changed. Hand the copy to TravelField(..., unknown_free = false). Neither
+  // touches the volume. Not available on a sharded volume, like the distance field.
+  FreeLayer MakeFreeLayer(const BoundingCube<float>& volumn) const;
+  void ObserveFree(FreeLayer& layer, const Mat& img_depth, float max_depth, const CameraIntrinsics<float>& intrinsics,
+                   const SE3<float>& cam_T_world);
+  struct DistanceField ApplyFree(const FreeLayer& layer, const struct DistanceField& field,
+                                 int64_t* promoted = nullptr);
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

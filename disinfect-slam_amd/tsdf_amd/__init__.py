@@ -1216,6 +1216,79 @@ class Engine:
             k0 += n
         return out
 
+    # ---- observed free space ----
+    def _free_box(self, layer):
+        """(tsdf_free_box, the layer's words as the calls take them, whether they are device memory)."""
+        o, d = [int(v) for v in layer["origin"]], [int(v) for v in layer["dims"]]
+        if len(o) != 3 or len(d) != 3:
+            raise ValueError("a layer's origin and dims are three integers each")
+        bits = layer["bits"]
+        device = _is_torch_cuda(bits)
+        if device:
+            import torch
+            if bits.dtype != torch.int32 or not bits.is_contiguous():
+                raise ValueError("a device layer's bits are a contiguous torch.int32 tensor")
+            n = bits.numel()
+        else:
+            if not (isinstance(bits, np.ndarray) and bits.dtype == np.uint32 and bits.flags.c_contiguous):
+                raise ValueError("a host layer's bits are a contiguous numpy uint32 array")
+            n = bits.size
+        if n != max(d[2], 0) * max(d[1], 0) * ((max(d[0], 0) + 31) // 32):
+            raise ValueError("the layer's bits do not match its dims: nz * ny * ceil(nx / 32) words")
+        return _lib.FreeBox((C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d)), bits, device
+
+    def free_observe(self, layer, depth, K, cam_T_world: SE3, max_depth: float):
+        """Marks in `layer` (esdf.free_layer) every voxel of its box that this depth frame saw as free
+        (tsdf_free_observe): the voxel update's own projection, with sdf >= truncation and the voxel in front
+        of the camera plane, whether or not the voxel's block exists. bits |= free: idempotent and monotone.
+        depth: (H, W) float32, a host array or a device tensor; it is moved to where the layer's bits are.
+        A device layer's call is asynchronous on the engine stream. Does not touch the volume: pending
+        frames stay pending, and a shard engine serves as well. Returns the layer."""
+        L = _lib.load()
+        box, bits, device = self._free_box(layer)
+        if device:
+            import torch
+            dp = depth if _is_torch_cuda(depth) else torch.as_tensor(np.ascontiguousarray(depth, dtype=np.float32),
+                                                                     device=bits.device)
+            if dp.dtype != torch.float32:
+                raise ValueError("free_observe: depth must be float32")
+            dp = dp.contiguous()
+        else:
+            dp = np.ascontiguousarray(depth.cpu().numpy() if _is_torch_cuda(depth) else depth, dtype=np.float32)
+        if dp.ndim != 2:
+            raise ValueError("free_observe: depth is (H, W)")
+        h, w = int(dp.shape[0]), int(dp.shape[1])
+        Kc = K._c() if isinstance(K, CameraIntrinsics) else _lib.Intrinsics(*[float(v) for v in K])
+        self._wait_torch(bits, dp)
+        rc = L.tsdf_free_observe(self._h, C.byref(box), _ptr(bits), _ptr(dp), w, h,
+                                 TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(Kc),
+                                 C.byref(cam_T_world._c()), float(max_depth))
+        self._signal_torch(bits, dp)
+        _lib.check(rc, "tsdf_free_observe")
+        return layer
+
+    def free_apply(self, layer, field, count: bool = True):
+        """A distance field with its state promoted from 0 (unobserved) to 1 (free) wherever the layer's
+        bit is set (tsdf_free_apply); states 1 and 2 and voxels outside the layer's box stay. Returns a new
+        field dict: `state` a promoted copy where the layer's bits are (numpy for a host layer, a tensor
+        for a device layer), `promoted` the number of voxels changed (None with count=False, which keeps a
+        device call asynchronous), everything else -- d2 included -- shared with `field`. Hand it to
+        travel_field(..., unknown_free=False)."""
+        L = _lib.load()
+        box, bits, device = self._free_box(layer)
+        if field.get("state") is None:
+            raise ValueError("free_apply: the field has no state (distance_field(..., state=True))")
+        o, d = [int(v) for v in field["origin"]], [int(v) for v in field["dims"]]
+        st = self._box_array(field["state"], np.uint8, (d[2], d[1], d[0]), device, "state")
+        st = st.clone() if device else st.copy()
+        n = C.c_int64(0)
+        self._wait_torch(bits, st)
+        rc = L.tsdf_free_apply(self._h, C.byref(box), _ptr(bits), (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d), _ptr(st),
+                               TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(n) if count else None)
+        self._signal_torch(bits, st)
+        _lib.check(rc, "tsdf_free_apply")
+        return dict(field, state=st, promoted=int(n.value) if count else None)
+
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()
         b = None if bounds is None else np.ascontiguousarray(

@@ -202,6 +202,11 @@ class TravelConfig(C.Structure):
 
 TSDF_TRAVEL_UNREACHED = 0xFFFFFFFF
 
+
+class FreeBox(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3)]
+
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -227,6 +232,7 @@ EXPORTS = [
     "tsdf_edt_config_default", "tsdf_distance_field",
     "tsdf_uv_irradiance", "tsdf_uv_plan_config_default", "tsdf_uv_plan",
     "tsdf_travel_config_default", "tsdf_travel_field", "tsdf_travel_paths",
+    "tsdf_free_words", "tsdf_free_observe", "tsdf_free_apply",
 ]
 
 _lib = None
@@ -325,6 +331,12 @@ def load(path: str | None = None):
     L.tsdf_travel_field.argtypes = [P, C.POINTER(TravelConfig), P, P, P, C.c_int32, P, i, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32)]
     L.tsdf_travel_paths.argtypes = [P, C.POINTER(C.c_int32), P, i, P, C.c_int32, C.c_int32, P, P]
+    L.tsdf_free_words.argtypes = [C.POINTER(C.c_int32)]
+    L.tsdf_free_words.restype = C.c_int64
+    L.tsdf_free_observe.argtypes = [P, C.POINTER(FreeBox), P, P, i, i, i, C.POINTER(Intrinsics), C.POINTER(Pose),
+                                    C.c_float]
+    L.tsdf_free_apply.argtypes = [P, C.POINTER(FreeBox), P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, i,
+                                  C.POINTER(C.c_int64)]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -373,7 +385,8 @@ def load(path: str | None = None):
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
                  "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
-                 "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths"):
+                 "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths",
+                 "tsdf_free_observe", "tsdf_free_apply"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -122,3 +122,38 @@ def path_points(travel, voxel: float, path) -> np.ndarray:
     nx, ny, _ = travel["dims"]
     v = np.stack([p % nx, p // nx % ny, p // (nx * ny)], -1) + np.asarray(travel["origin"], np.int64)
     return (v.astype(np.float32) * np.float32(voxel)).astype(np.float32)
+
+
+# ---- observed free space (Engine.free_observe / free_apply; DESIGN.md "Observed free space") ----
+# A layer is a dict: bits (nz, ny, ceil(nx / 32)) -- numpy uint32 on the host, torch.int32 viewing the same bits
+# on a device -- origin and dims of its box in global voxels. Voxel (x, y, z) of the box is bit x & 31 of
+# bits[z, y, x >> 5].
+def free_layer(origin, dims, device=False):
+    """A cleared layer over the box origin (x, y, z), dims (nx, ny, nz): host words, or with device=True (or
+    a torch device) a tensor on that GPU."""
+    o, d = tuple(int(v) for v in origin), tuple(int(v) for v in dims)
+    if len(o) != 3 or len(d) != 3 or min(d) < 1:
+        raise ValueError("free_layer: origin and dims are three integers each, dims positive")
+    shape = (d[2], d[1], (d[0] + 31) // 32)
+    if device is False or device is None:
+        bits = np.zeros(shape, np.uint32)
+    else:
+        import torch
+        bits = torch.zeros(shape, dtype=torch.int32, device="cuda" if device is True else device)
+    return dict(bits=bits, origin=o, dims=d)
+
+
+def free_mask(layer) -> np.ndarray:
+    """bool (nz, ny, nx): the voxels of the layer's box that were observed free."""
+    b = layer["bits"]
+    b = b.cpu().numpy() if hasattr(b, "is_cuda") else np.asarray(b)
+    w = np.ascontiguousarray(b).view(np.uint32)
+    nx = int(layer["dims"][0])
+    m = (w[..., None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)
+    return m.reshape(w.shape[0], w.shape[1], -1)[..., :nx].astype(bool)
+
+
+def free_fraction(layer) -> float:
+    """The fraction of the box's voxels observed free."""
+    m = free_mask(layer)
+    return float(m.sum()) / float(m.size)

@@ -728,6 +728,65 @@ int tsdf_travel_paths(tsdf_engine* e, const int32_t dims[3], const uint32_t* cos
                       const int32_t* targets /* host, T x 3 box-local */, int32_t T, int32_t max_len,
                       int32_t* path /* host, T x max_len linear voxel indices */, int32_t* len /* host, T */);
 
+/* ---- Observed free space: a bit per voxel of a box, set by depth frames (no reference counterpart) ----
+ * The volume holds blocks near surfaces only, so the open interior of a room is state 0 (unobserved) in every
+ * distance field. Every depth frame carries the evidence that the space its rays crossed is empty; these calls
+ * keep it, whether or not a voxel's block exists, and promote a distance field's state with it, so that
+ * tsdf_travel_field(..., unknown_free = 0) floods exactly the space that was observed empty and a gap in a
+ * wall nobody looked through does not leak.
+ *
+ * The test is the voxel update's own geometry with one more condition. For the voxel g = (gx, gy, gz) in
+ * global voxel coordinates and a frame (depth W x H, K, cam_T_world, max_depth), with the engine's
+ * voxel_size and truncation:
+ *   pw = (float)g * voxel;  pc = cam_T_world * pw        (Eigen's order: SE3::Apply over _transformVector)
+ *   hx = fx pc.x + cx pc.z;  hy = fy pc.y + cy pc.z;  hz = pc.z
+ *   u = f2i(roundf(hx / hz));  v = f2i(roundf(hy / hz))  (half away from zero; the conversion truncates,
+ *                                                         saturates and turns NaN into 0)
+ *   in image: 0 <= u < W and 0 <= v < H;  d = depth[v W + u];  valid: d != 0 and d <= max_depth
+ *   range = |Kinv (u, v, 1)|: x = (1 / fx) u + (-cx (1 / fx)) 1, y likewise, sqrt(x x + (y y + 1 1))
+ *   sdf = range (d - hz)
+ *   free(g, frame) = in image && valid && sdf >= truncation && hz > 0
+ * all in float32, one IEEE operation at a time with no contraction: the same operations in the same order
+ * as the update. sdf >= truncation is the update's fminf(1, sdf / truncation) == 1: had the voxel's block
+ * existed and been empty, this frame would have written tsdf exactly 1 into it. hz > 0 is new and
+ * deliberate: the update also touches voxels behind the camera plane whose quotient happens to land in the
+ * image, and a safety layer must not call those observed. A NaN sdf fails >=, so it is not free. The camera
+ * centre has hz = 0 and is never marked: a caller seeds a travel field at a voxel in front of the camera.
+ *
+ * A layer is the caller's: a box (origin and dims in global voxels) and uint32_t bits[nz * ny * wx] with
+ * wx = ceil(nx / 32). Voxel (x, y, z) of the box is bit x & 31 of word (z * ny + y) * wx + (x >> 5). The
+ * library never sets the padding bits of a row's last word. A cleared layer is all zeros.
+ * tsdf_free_words: the number of words, nz * ny * ceil(nx / 32); 0 for invalid dims.
+ * tsdf_free_observe: bits |= free(., frame) over the box. Idempotent and monotone: bits are only ever set,
+ * and a frame observed twice changes nothing. It does not depend on TSDF_FREE_CULL (an A/B and test knob
+ * read at tsdf_create: 0 disables the two exact culls of the kernel).
+ * tsdf_free_apply: state[v] = 1 wherever state[v] == 0, v lies inside the layer's box and its bit is set,
+ * for every voxel v of the state array's box (origin, dims; nz * ny * nx bytes, x fastest: a distance
+ * field's). States 1 and 2, and voxels outside the layer's box, stay as they are: an inside voxel is never
+ * promoted. The two boxes may overlap partly, nest or be disjoint. *promoted is the number of voxels changed.
+ * Required, of the layer's box and of apply's state box alike: each dims[i] in 1 .. 2048, nx * ny * nz <=
+ * 2^28, every voxel in a block of the int16 block range (origin >> 3 >= -32768, (origin + dims - 1) >> 3 <=
+ * 32767); width / height in 1 .. the engine's max_width / max_height; max_depth > 0; mem_kind one of the
+ * two; every pointer non-NULL except promoted. Anything else is TSDF_ERR_INVALID_ARG with nothing written.
+ * Neither call touches the volume: the engine lends its stream and scratch (grown on demand, freed by
+ * tsdf_destroy), no status bits are set, pending pipelined frames stay pending -- the natural use is one
+ * observe per integrated frame -- and a shard engine (shard_count > 1) serves as well as any other.
+ * Device memory (bits and depth, or bits and state, alike): observe is asynchronous on the engine stream,
+ * and its inputs must stay valid until the next engine call or tsdf_synchronize; apply is asynchronous when
+ * promoted is NULL, else it synchronises the engine stream once. Host memory: the call copies up, runs,
+ * copies down and synchronises. K, cam_T_world, box, origin, dims and promoted are host memory. */
+typedef struct tsdf_free_box {
+  int32_t origin[3]; /* global voxel coordinates of the box's first voxel */
+  int32_t dims[3];   /* nx, ny, nz */
+} tsdf_free_box;
+int64_t tsdf_free_words(const int32_t dims[3]);
+int tsdf_free_observe(tsdf_engine* e, const tsdf_free_box* box, uint32_t* bits, const float* depth, int width,
+                      int height, int mem_kind /* bits and depth alike */, const tsdf_intrinsics* K,
+                      const tsdf_pose* cam_T_world, float max_depth);
+int tsdf_free_apply(tsdf_engine* e, const tsdf_free_box* box, const uint32_t* bits, const int32_t origin[3],
+                    const int32_t dims[3], uint8_t* state, int mem_kind /* bits and state alike */,
+                    int64_t* promoted /* host, may be NULL */);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
