@@ -1,5 +1,5 @@
 // tsdf_host_track.hip -- pose tracking (DESIGN.md "Pose tracking"; kernels in tsdf_track.hip, host
-// math in tsdf_track_host.h): tsdf_raycast_surface, tsdf_icp_linearize, tsdf_track.
+// math in tsdf_track_host.h): tsdf_raycast_surface, tsdf_icp_linearize, tsdf_point_map_normals, tsdf_track.
 #include <cmath>
 #include <string>
 
@@ -31,6 +31,16 @@ int surface_launch(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const
   const dim3 grid((W + 15) / 16, (H + 15) / 16);
   hipLaunchKernelGGL(k_raycast_surface, grid, dim3(256), V.n ? (size_t)V.nw * 4 : 0, e->stream, e->D, P, step, V, S);
   LAUNCH_OK("k_raycast_surface");
+  return TSDF_OK;
+}
+
+// tsdf_track's model normals `out` from the device maps of camera (K, W x H, pose): k_surface_normals on
+// the engine stream (the kernel reads wt and the size of the camera alone)
+int normals_launch(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const tsdf_pose* pose, float max_depth,
+                   const float* point, const float* normal, float* out) {
+  hipLaunchKernelGGL(k_surface_normals, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, e->stream,
+                     make_params(e, K, W, H, pose, max_depth), point, normal, out);
+  LAUNCH_OK("k_surface_normals");
   return TSDF_OK;
 }
 
@@ -129,6 +139,33 @@ int tsdf_icp_linearize(tsdf_engine* e, const float* depth, int W, int H, const t
                     max_dist, max_depth, out29);
 }
 
+int tsdf_point_map_normals(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H, const tsdf_pose* pose,
+                           const float* point, const float* normal, float* out, int mem_kind) {
+  TraceRange trace_("tsdf_point_map_normals");
+  if (!e || !frame_args_ok(e, K, pose, W, H) || !point || !normal || !out || !mem_kind_ok(mem_kind)) {
+    set_error("tsdf_point_map_normals: invalid argument");
+    return TSDF_ERR_INVALID_ARG;
+  }
+  if (track_refused(e, "tsdf_point_map_normals")) return TSDF_ERR_INVALID_ARG;
+  HIP_OK(hipSetDevice(e->device));
+  ENTER(e);
+  const float max_depth = 1.0f;  // not read by the kernel
+  if (mem_kind == TSDF_MEM_DEVICE) return normals_launch(e, K, W, H, pose, max_depth, point, normal, out);
+  // host maps: staged (sections 16-byte aligned), the result copied out
+  const size_t n = (size_t)W * H, o_nr = up16(n * 12), o_out = o_nr + up16(n * 12);
+  int rc = track_stage(e, o_out + up16(n * 12));
+  if (rc) return rc;
+  uint8_t* b = e->tk_stage;
+  HIP_OK(hipMemcpyAsync(b, point, n * 12, hipMemcpyHostToDevice, e->stream));
+  HIP_OK(hipMemcpyAsync(b + o_nr, normal, n * 12, hipMemcpyHostToDevice, e->stream));
+  rc = normals_launch(e, K, W, H, pose, max_depth, reinterpret_cast<const float*>(b),
+                      reinterpret_cast<const float*>(b + o_nr), reinterpret_cast<float*>(b + o_out));
+  if (rc) return rc;
+  HIP_OK(hipMemcpyAsync(out, b + o_out, n * 12, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return TSDF_OK;
+}
+
 void tsdf_track_config_default(tsdf_track_config* c) {
   if (!c) return;
   *c = tsdf_track_config{};
@@ -177,10 +214,8 @@ int tsdf_track(tsdf_engine* e, const float* depth, int W, int H, int mem_kind, c
   int rc = surface_launch(e, K, W, H, guess, max_depth, SurfaceOut{e->tk_point, e->tk_normal, nullptr, nullptr, nullptr});
   if (rc) return rc;
   // the normals the loop uses come from the model's points (k_surface_normals: why)
-  hipLaunchKernelGGL(k_surface_normals, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, e->stream,
-                     make_params(e, K, W, H, guess, max_depth), (const float*)e->tk_point, (const float*)e->tk_normal,
-                     e->tk_pnormal);
-  LAUNCH_OK("k_surface_normals");
+  rc = normals_launch(e, K, W, H, guess, max_depth, e->tk_point, e->tk_normal, e->tk_pnormal);
+  if (rc) return rc;
   tsdf_pose est = *guess;
   tsdf_track_result r{};
   r.status = TSDF_TRACK_OK;

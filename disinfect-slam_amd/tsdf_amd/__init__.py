@@ -876,6 +876,10 @@ class Engine:
         if dev != _is_torch_cuda(pt) or dev != _is_torch_cuda(nr):
             raise ValueError("depth and the model maps must be all host or all device")
         if dev:
+            import torch
+            for a in (depth, pt, nr):
+                if a.dtype != torch.float32 or a.device.index != self.device:
+                    raise ValueError("device depth and maps must be float32 tensors on this engine's GPU")
             d, pt, nr = depth.contiguous(), pt.contiguous(), nr.contiguous()
         else:
             d, pt, nr = _np(depth, np.float32), _np(pt, np.float32), _np(nr, np.float32)
@@ -893,6 +897,37 @@ class Engine:
         A[np.triu_indices(6)] = out[:21]
         A = A + np.triu(A, 1).T
         return A, out[21:27].copy(), float(out[27]), int(out[28])
+
+    def point_map_normals(self, model: dict, K, cam_T_world: SE3):
+        """The model normals track() uses (tsdf_point_map_normals), from the point / normal maps (h, w, 3)
+        f32 of raycast_surface(K, w, h, cam_T_world, ...): the cross product of the points' central
+        differences, turned to face the camera, over its length; zeros on the border, beside a hole and
+        more than acos(0.3) off the viewing ray. model["normal"] says only where a surface is. Returns
+        (h, w, 3) f32: a numpy array for numpy maps, a torch tensor on this engine's GPU for device maps."""
+        pt, nr = model["point"], model["normal"]
+        dev = _is_torch_cuda(pt)
+        if dev != _is_torch_cuda(nr):
+            raise ValueError("the model maps must be all host or all device")
+        if dev:
+            import torch
+            for a in (pt, nr):
+                if a.dtype != torch.float32 or a.device.index != self.device:
+                    raise ValueError("device maps must be float32 tensors on this engine's GPU")
+            pt, nr = pt.contiguous(), nr.contiguous()
+            out = torch.empty_like(pt)
+        else:
+            pt, nr = _np(pt, np.float32), _np(nr, np.float32)
+            out = np.zeros(pt.shape, np.float32)
+        if pt.ndim != 3 or pt.shape[2] != 3 or tuple(nr.shape) != tuple(pt.shape):
+            raise ValueError("point and normal must both be (h, w, 3)")
+        h, w = pt.shape[:2]
+        self._wait_torch(pt, nr, out)
+        _lib.check(_lib.load().tsdf_point_map_normals(self._h, C.byref(self._Kc(K)), w, h, C.byref(cam_T_world._c()),
+                                                      _ptr(pt), _ptr(nr), _ptr(out),
+                                                      TSDF_MEM_DEVICE if dev else TSDF_MEM_HOST),
+                   "tsdf_point_map_normals")
+        self._signal_torch(pt, nr, out)
+        return out
 
     def track(self, depth, K, guess: SE3, max_depth: float, **cfg):
         """The pose of a depth frame (h, w) f32 against the volume (tsdf_track): frame-to-model

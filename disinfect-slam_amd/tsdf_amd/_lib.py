@@ -228,6 +228,7 @@ EXPORTS = [
     "tsdf_group_stream_signal",
     "tsdf_extract_mesh_indexed",
     "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track_config_default", "tsdf_track",
+    "tsdf_point_map_normals",
     "tsdf_uv_config_default", "tsdf_surface_normals", "tsdf_uv_dose",
     "tsdf_edt_config_default", "tsdf_distance_field",
     "tsdf_uv_irradiance", "tsdf_uv_plan_config_default", "tsdf_uv_plan",
@@ -315,6 +316,7 @@ def load(path: str | None = None):
     L.tsdf_track_config_default.restype = None
     L.tsdf_track.argtypes = [P, P, i, i, i, C.POINTER(Intrinsics), C.POINTER(Pose), f, C.POINTER(TrackConfig),
                              C.POINTER(TrackResult)]
+    L.tsdf_point_map_normals.argtypes = [P, C.POINTER(Intrinsics), i, i, C.POINTER(Pose), P, P, P, i]
     L.tsdf_uv_config_default.argtypes = [P, C.POINTER(UvConfig)]
     L.tsdf_uv_config_default.restype = None
     L.tsdf_surface_normals.argtypes = [P, P, i64, f, P, i]
@@ -384,7 +386,7 @@ def load(path: str | None = None):
                  "tsdf_group_flush", "tsdf_group_synchronize", "tsdf_group_shard", "tsdf_group_get_stats",
                  "tsdf_group_query", "tsdf_group_raycast", "tsdf_group_stream_signal",
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
-                 "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
+                 "tsdf_point_map_normals", "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
                  "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths",
                  "tsdf_free_observe", "tsdf_free_apply"):
         getattr(L, name).restype = C.c_int

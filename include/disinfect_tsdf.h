@@ -442,7 +442,7 @@ int tsdf_extract_mesh_indexed(tsdf_engine* e, const float* bounds, float missing
                               const tsdf_mesh_out* out, int64_t* num_vertices, int64_t* num_triangles);
 
 /* ---- Pose tracking against the volume (frame-to-model point-to-plane ICP, KinectFusion style) ----
- * All three calls complete a pending pipelined frame first and are not available on a shard engine
+ * All four calls complete a pending pipelined frame first and are not available on a shard engine
  * (shard_count > 1): TSDF_ERR_INVALID_ARG.
  *
  * tsdf_raycast_surface: what tsdf_raycast sees, as float maps. The march is tsdf_raycast's (view grid,
@@ -522,6 +522,19 @@ typedef struct tsdf_track_result {
 int tsdf_track(tsdf_engine* e, const float* depth, int width, int height, int mem_kind,
                const tsdf_intrinsics* K, const tsdf_pose* guess_cam_T_world, float max_depth,
                const tsdf_track_config* cfg /* NULL = defaults */, tsdf_track_result* out);
+
+/* tsdf_point_map_normals: tsdf_track's model normals as a call, for a loop composed of
+ * tsdf_raycast_surface and tsdf_icp_linearize. point and normal are the H x W x 3 maps of a
+ * tsdf_raycast_surface call from (K, width, height, cam_T_world); normal says only where a surface is
+ * (any component != 0). out (H x W x 3) receives the normals by tsdf_track's rule above, fp32 one
+ * operation at a time: with to = p - camera centre and c turned so that c . to <= 0, a pixel keeps
+ * c / sqrt(c . c) if c . c > 0 and finite and (c . to)^2 >= 0.3^2 * ((c . c) * (to . to)); zeros elsewhere.
+ * Of the camera only its centre and the size are used. The three maps are host or device memory, all
+ * alike (mem_kind). out must not overlap point or normal: a pixel reads its neighbours' points while
+ * others are written. It is the launch tsdf_track makes. */
+int tsdf_point_map_normals(tsdf_engine* e, const tsdf_intrinsics* K, int width, int height,
+                           const tsdf_pose* cam_T_world, const float* point, const float* normal,
+                           float* out, int mem_kind);
 
 /* ---- UV dose on surface points (no reference counterpart: its planner receives the mesh over ROS and
  * irradiates off-board) ----

@@ -1,6 +1,7 @@
 """numpy restatements of the pose-tracking contract (include/disinfect_tsdf.h, DESIGN.md "Pose
-tracking") for tests/test_gpu_surface.py and tests/test_gpu_icp.py: the raycast's surface maps from an
-engine dump, the per-pixel rules of one ICP linearisation, and the Gauss-Newton loop around them.
+tracking") for tests/test_gpu_surface.py, tests/test_gpu_icp.py and tests/test_gpu_icp_edges.py: the
+raycast's surface maps from an engine dump, the per-pixel rules of one ICP linearisation, and the
+Gauss-Newton loop around them.
 Per-pixel arithmetic is float32 one operation at a time, as the kernels' (no contraction, IEEE
 division and square root); sums, solve and pose update are float64."""
 import math
@@ -188,9 +189,14 @@ def point_map_normals(model, K, pose):
     return dict(point=pt, normal=out)
 
 
-def icp_terms(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_depth=MAX_DEPTH):
-    """(J (n, 6) float64, r (n,) float64) of the kept pixels by the per-pixel rules of tsdf_icp_linearize,
-    computed in float32."""
+def icp_terms_full(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_depth=MAX_DEPTH,
+                   d_positive=True):
+    """Every sample of the stride lattice in sample order (sample s is pixel (stride * (s % nsx),
+    stride * (s // nsx))) by the per-pixel rules of tsdf_icp_linearize, computed in float32: dict of keep
+    (n,) bool, J (n, 6) float64 and r (n,) float64 (float32 values; whatever the arithmetic gives where
+    keep is false), um, vm (n,) int64 the model pixel read (0 where the sample is dropped before the
+    read), u, v (n,) the depth pixel, nsx. d_positive=False leaves the gate d > 0 out: only for
+    tests/test_icp_cases_cpu.py, to show which cases that gate alone decides."""
     H, W = depth.shape
     F, M = Camera(K, pose), Camera(model_K, model_pose)
     pt, nm = model["point"], model["normal"]
@@ -198,7 +204,7 @@ def icp_terms(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_
     v, u = [a.reshape(-1) for a in np.meshgrid(np.arange(0, H, stride), np.arange(0, W, stride), indexing="ij")]
     d = depth[v, u].astype(f32)
     with np.errstate(all="ignore"):
-        keep = (d > 0) & (d <= f32(max_depth))
+        keep = (d <= f32(max_depth)) & ((d > 0) if d_positive else True)
         ray = F.pixel_ray(u, v)
         pc = (ray[0] * d, ray[1] * d, d)
         pw = se3_apply(F.wq, F.wt, pc)
@@ -217,8 +223,52 @@ def icp_terms(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_
         r = dot3(n, e)
         c = cross3(pw, n)
     assert r.dtype == f32 and c[0].dtype == f32
-    J = np.stack([*c, *n], -1)[keep].astype(np.float64)
-    return J, r[keep].astype(np.float64)
+    return dict(keep=keep, J=np.stack([*c, *n], -1).astype(np.float64), r=r.astype(np.float64), um=um, vm=vm,
+                u=u, v=v, nsx=len(range(0, W, stride)))
+
+
+def icp_terms(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_depth=MAX_DEPTH):
+    """(J (n, 6) float64, r (n,) float64) of the kept pixels by the per-pixel rules of tsdf_icp_linearize,
+    computed in float32."""
+    t = icp_terms_full(depth, K, pose, model, model_K, model_pose, stride, max_dist, max_depth)
+    return t["J"][t["keep"]], t["r"][t["keep"]]
+
+
+def icp_lane_terms(J, r, keep):
+    """The 29 double terms of every sample, (n, 29): the products of J and r as the kernel forms them
+    (exact), +0.0 where the sample is gated."""
+    J = np.where(keep[:, None], J, 0.0)
+    r = np.where(keep, r, 0.0)
+    cols = [J[:, i] * J[:, j] for i in range(6) for j in range(i, 6)] + [J[:, i] * r for i in range(6)] + [r * r]
+    return np.stack(cols + [keep.astype(np.float64)], -1)
+
+
+def icp_tree(J, r, keep, nsamples):
+    """The 29 sums by the documented addition tree (csrc/tsdf_track.hip, DESIGN.md "Pose tracking"), in
+    float64: per lane the 29 terms (+0.0 where gated or past nsamples); per wave of 64 the xor butterfly
+    over 32, 16, 8, 4, 2, 1 (a = a + a[lane ^ o]), lane 0's value; per workgroup of 256
+    ((w0 + w1) + w2) + w3; then 32 runs of ceil(nwg / 32) consecutive workgroups, each added from 0.0
+    in index order; then the runs from 0.0 in index order."""
+    assert J.shape[0] == r.shape[0] == keep.shape[0] == nsamples
+    nwg = (nsamples + 255) // 256
+    a = np.zeros((nwg * 256, 29))
+    a[:nsamples] = icp_lane_terms(J, r, keep)
+    a = a.reshape(nwg, 4, 64, 29)
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        a = a + a[:, :, lane ^ o]
+    w = a[:, :, 0]
+    part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    ln = (nwg + 31) // 32
+    runs = np.zeros((32, 29))
+    for k in range(ln):  # the k-th workgroup of every run that has one
+        g = np.arange(32) * ln + k
+        ok = g < np.minimum(nwg, (np.arange(32) + 1) * ln)
+        runs[ok] = runs[ok] + part[g[ok]]
+    out = np.zeros(29)
+    for c in range(32):
+        out = out + runs[c]
+    return out
 
 
 def icp_sums_exact(J, r):
@@ -276,12 +326,16 @@ def pose_update(pose, xi):
 
 
 def track(eng, depth, K, guess, max_depth=MAX_DEPTH, levels=3, stride=(4, 2, 1), iterations=(4, 5, 10),
-          max_dist=0.1, min_inliers=6):
+          max_dist=0.1, min_inliers=6, eps_rot=0.0, eps_trans=0.0, norms=None):
     """tsdf_track's loop in numpy: the model maps from the engine, the per-pixel rules above, float64
-    sums, numpy.linalg.cholesky. Returns (pose, status, iterations, inliers, rmse)."""
+    sums, numpy.linalg.cholesky; after an update a level ends when |omega| <= eps_rot and |t| <= eps_trans
+    (eps as floats, as the engine holds them), if either eps is greater than 0. Returns (pose, status,
+    iterations, inliers, rmse); `norms`, a list, receives (level, |omega|, |t|) of every iteration."""
     H, W = depth.shape
     model = point_map_normals(eng.raycast_surface(K, W, H, guess, max_depth, maps=()), K, guess)
     est, done, inl, rmse = guess, 0, 0, 0.0
+    eps_rot, eps_trans = float(f32(eps_rot)), float(f32(eps_trans))
+    early = eps_rot > 0 or eps_trans > 0
     for l in range(levels):
         for _ in range(iterations[l]):
             J, r = icp_terms(depth, K, est, model, K, guess, stride[l], max_dist, max_depth)
@@ -298,6 +352,11 @@ def track(eng, depth, K, guess, max_depth=MAX_DEPTH, levels=3, stride=(4, 2, 1),
                 return est, 1, done, inl, rmse
             est = pose_update(est, xi)
             done += 1
+            nw, nt = math.sqrt(float(xi[:3] @ xi[:3])), math.sqrt(float(xi[3:] @ xi[3:]))
+            if norms is not None:
+                norms.append((l, nw, nt))
+            if early and nw <= eps_rot and nt <= eps_trans:
+                break
     return est, 0, done, inl, rmse
 
 
