@@ -312,6 +312,10 @@ struct tsdf_engine {
   // or an apply's counter, then, for host arrays, their staging, one section each. Grow-only. (Last, as
   // tv_buf was: the frame path's fields keep their offsets.)
   DevBuf<uint8_t> fr_buf;
+  // frontiers and components (tsdf_frontier_mark / tsdf_components; tsdf_host_frontier.hip): the control
+  // words, a slot per voxel, the host arrays' staging, then accumulators and records per component, one
+  // section each. Grow-only. (Last, as fr_buf was.)
+  DevBuf<uint8_t> cc_buf;
 
   tsdf_engine() = default;
   // D's buffers, the pinned mirrors, events and streams; the scratch above frees itself. The caller has

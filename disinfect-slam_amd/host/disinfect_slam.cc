@@ -83,6 +83,10 @@ DistanceField DISINFSystem::query_free_space(const DistanceField& field, int64_t
   return TSDF_->ApplyFreeSpace(field, promoted);
 }
 
+FrontierSet DISINFSystem::query_frontiers(const DistanceField& field, const TravelField* travel, int min_size) {
+  return TSDF_->Frontiers(field, travel, min_size);
+}
+
 void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {
   const size_t nv = mesh.verts.size() / 3;
   if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);

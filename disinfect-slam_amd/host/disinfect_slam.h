@@ -80,6 +80,12 @@ class DISINFSystem {
   // never marked: start from a position in front of the camera. Without enable_free_space nothing changes.
   void enable_free_space(const BoundingCube<float>& volumn);
   DistanceField query_free_space(const DistanceField& field, int64_t* promoted = nullptr);
+  // Where the map ends (DESIGN.md "Frontiers and components"): the observed-free voxels of `field` that touch
+  // unobserved space and that `travel` (over the same box; may be null) reached, clustered into 26-connected
+  // components of at least min_size voxels. Each cluster carries its size, bounding box, coordinate sums and
+  // its goal: the member cheapest to travel to, goal_key / 3 voxels away (frontier_goals in uv_dose.h gives
+  // world positions). field should come from query_free_space, over surface sites.
+  FrontierSet query_frontiers(const DistanceField& field, const TravelField* travel = nullptr, int min_size = 1);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

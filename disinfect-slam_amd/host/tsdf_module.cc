@@ -154,6 +154,21 @@ std::vector<std::vector<int32_t>> TSDFSystem::TravelPaths(const struct TravelFie
   return tsdf_.TravelPaths(travel, targets, max_len);
 }
 
+FrontierSet TSDFSystem::Frontiers(const struct DistanceField& field, const struct TravelField* travel, int min_size) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.Frontiers(field, travel, min_size);
+}
+
+FrontierSet TSDFSystem::Components(const std::vector<uint8_t>& mask, const int32_t origin[3], const int32_t dims[3],
+                                   const std::vector<uint32_t>& key, int min_size) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.Components(mask, origin, dims, key, min_size);
+}
+
 void TSDFSystem::EnableFreeSpace(const BoundingCube<float>& volumn) {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });

@@ -90,6 +90,11 @@ class TSDFSystem {
   std::vector<std::vector<int32_t>> TravelPaths(const struct TravelField& travel, const std::vector<int32_t>& targets,
                                                 int max_len = 4096);
   float voxel_size() const { return tsdf_.voxel_size(); }
+  // frontiers and components (TSDFGrid::Frontiers / Components), after every queued frame
+  FrontierSet Frontiers(const struct DistanceField& field, const struct TravelField* travel = nullptr,
+                        int min_size = 1);
+  FrontierSet Components(const std::vector<uint8_t>& mask, const int32_t origin[3], const int32_t dims[3],
+                         const std::vector<uint32_t>& key = {}, int min_size = 1);
   // Observed free space (TSDFGrid::ObserveFree / ApplyFree). EnableFreeSpace: from the next queued frame on,
   // the worker also observes every frame it integrates into a layer over `volumn` that the system owns (a raw
   // frame's half-size depth is taken from HalfRGBD once more); calling it again starts a cleared layer.

@@ -260,6 +260,32 @@ struct TravelField {
   size_t at(int x, int y, int z) const { return ((size_t)z * dims[1] + y) * dims[0] + x; }
 };
 
+// Clusters of a voxel mask over a box (tsdf_components), and with `mask` the frontier they cluster
+// (tsdf_frontier_mark): observed-free, reachable voxels that touch unobserved space. label is the least linear
+// index of each voxel's 26-connected component, TSDF_COMPONENT_NONE off the mask; clusters are the components
+// with at least min_size voxels in ascending label, `total` counts all of them. Voxel (x, y, z) of the box is
+// global voxel origin + (x, y, z).
+// One cluster: tsdf_component, field for field (this header does not need the C header; voxel_tsdf.cc asserts it).
+struct FrontierCluster {
+  uint32_t label;     // least linear index (z * ny + y) * nx + x of the component
+  uint32_t size;      // voxels
+  int32_t lo[3];      // box-local bounding box, x y z, inclusive
+  int32_t hi[3];
+  int64_t sum[3];     // sums of the members' box-local x, y, z: centroid = sum / size
+  uint32_t goal;      // linear index of the member with the least key, ties to the least index
+  uint32_t goal_key;  // its key: a travel cost, goal_key / 3 voxels of travel
+};
+struct FrontierSet {
+  int32_t origin[3] = {0, 0, 0};
+  int32_t dims[3] = {0, 0, 0};           // nx, ny, nz
+  std::vector<uint8_t> mask;             // nz * ny * nx, x fastest
+  std::vector<uint32_t> label;           // same shape
+  std::vector<FrontierCluster> clusters; // size >= min_size, ascending label
+  int64_t marked = 0;                    // ones in mask
+  int32_t total = 0;                     // components of any size
+  size_t at(int x, int y, int z) const { return ((size_t)z * dims[1] + y) * dims[0] + x; }
+};
+
 // An observed-free-space layer (tsdf_free_observe / tsdf_free_apply): a bit per voxel of a box, set when a
 // depth frame saw the voxel as free. Voxel (x, y, z) of the box is global voxel origin + (x, y, z) and bit
 // x & 31 of word (z * ny + y) * wx + (x >> 5), wx = ceil(nx / 32). Host memory: the facade carries no HIP

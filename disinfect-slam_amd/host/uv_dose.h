@@ -204,4 +204,27 @@ inline std::vector<float> reachable_candidates(const std::vector<float>& positio
   return out;
 }
 
+// ---- frontiers (tsdf_types.h FrontierSet; tsdf_amd.esdf.frontier_goals) ----
+// World positions of a frontier set's clusters, voxel v at v * voxel: per cluster seven floats -- the goal
+// (its cheapest voxel to travel to), the centroid (float(sum / size + origin) * voxel, the quotient in double)
+// and goal_key / 3 * voxel [m], the travel distance to the goal (0 without a travel field, infinity for a key
+// of TSDF_TRAVEL_UNREACHED).
+// (Cluster: tsdf_component or the facade's FrontierCluster.)
+template <typename Cluster>
+std::vector<float> frontier_goals(const std::vector<Cluster>& clusters, const int32_t origin[3], const int32_t dims[3],
+                                  float voxel) {
+  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) throw std::invalid_argument("frontier_goals: dims are positive");
+  std::vector<float> out;
+  out.reserve(7 * clusters.size());
+  for (const Cluster& c : clusters) {
+    const int64_t g = c.goal, nx = dims[0], ny = dims[1];
+    const int64_t v[3] = {g % nx + origin[0], g / nx % ny + origin[1], g / (nx * ny) + origin[2]};
+    for (int a = 0; a < 3; ++a) out.push_back((float)v[a] * voxel);
+    const double size = (double)(c.size > 0 ? c.size : 1u);
+    for (int a = 0; a < 3; ++a) out.push_back((float)((double)c.sum[a] / size + (double)origin[a]) * voxel);
+    out.push_back(c.goal_key == TSDF_TRAVEL_UNREACHED ? INFINITY : ((float)c.goal_key / 3.0f) * voxel);
+  }
+  return out;
+}
+
 }  // namespace disinfect

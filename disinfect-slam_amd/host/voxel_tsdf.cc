@@ -371,6 +371,71 @@ struct DistanceField TSDFGrid::ApplyFree(const FreeLayer& layer, const struct Di
   return out;
 }
 
+static_assert(sizeof(FrontierCluster) == sizeof(tsdf_component) && offsetof(FrontierCluster, lo) == offsetof(tsdf_component, lo) &&
+                  offsetof(FrontierCluster, hi) == offsetof(tsdf_component, hi) &&
+                  offsetof(FrontierCluster, sum) == offsetof(tsdf_component, sum) &&
+                  offsetof(FrontierCluster, goal) == offsetof(tsdf_component, goal) &&
+                  offsetof(FrontierCluster, goal_key) == offsetof(tsdf_component, goal_key),
+              "FrontierCluster is tsdf_component");
+
+FrontierSet TSDFGrid::Components(const std::vector<uint8_t>& mask, const int32_t origin[3], const int32_t dims[3],
+                                 const std::vector<uint32_t>& key, int min_size) {
+  if (group_) throw std::runtime_error("TSDFGrid::Components: not available on a sharded volume");
+  FrontierSet s;
+  tsdf_components_config c;
+  tsdf_components_config_default(&c);
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    s.origin[a] = origin[a];
+    c.dims[a] = s.dims[a] = dims[a];
+    n *= (size_t)std::max(dims[a], 0);
+  }
+  if (n == 0 || mask.size() != n || (!key.empty() && key.size() != n))
+    throw std::invalid_argument("TSDFGrid::Components: the mask (and the key) need an entry for every voxel of the box");
+  c.min_size = min_size;
+  s.mask = mask;
+  for (uint8_t m : mask) s.marked += m != 0;
+  s.label.resize(n);
+  // the two-call pattern with a first guess: a table too small asks again with the count it was told
+  int32_t count = 0, cap = 4096;
+  for (int attempt = 0;; ++attempt) {
+    s.clusters.assign((size_t)cap, FrontierCluster{});
+    const int rc = tsdf_components(engine_, &c, mask.data(), key.empty() ? nullptr : key.data(), s.label.data(),
+                                   TSDF_MEM_HOST, reinterpret_cast<tsdf_component*>(s.clusters.data()), cap, &count,
+                                   &s.total);
+    if (rc == TSDF_ERR_CAPACITY && attempt == 0) {
+      cap = count;
+      continue;
+    }
+    check_tsdf(rc, "tsdf_components");
+    break;
+  }
+  s.clusters.resize((size_t)count);
+  return s;
+}
+
+FrontierSet TSDFGrid::Frontiers(const struct DistanceField& field, const struct TravelField* travel, int min_size) {
+  if (group_) throw std::runtime_error("TSDFGrid::Frontiers: not available on a sharded volume");
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) n *= (size_t)std::max(field.dims[a], 0);
+  if (n == 0 || field.state.size() != n)
+    throw std::invalid_argument("TSDFGrid::Frontiers: the field needs a state for every voxel of its box");
+  if (travel) {
+    for (int a = 0; a < 3; ++a)
+      if (travel->origin[a] != field.origin[a] || travel->dims[a] != field.dims[a])
+        throw std::invalid_argument("TSDFGrid::Frontiers: the travel field's box is not the distance field's");
+    if (travel->cost.size() != n) throw std::invalid_argument("TSDFGrid::Frontiers: the travel field needs a cost per voxel");
+  }
+  std::vector<uint8_t> mask(n);
+  int64_t marked = 0;
+  check_tsdf(tsdf_frontier_mark(engine_, field.dims, field.state.data(), travel ? travel->cost.data() : nullptr,
+                                mask.data(), TSDF_MEM_HOST, &marked),
+             "tsdf_frontier_mark");
+  FrontierSet s = Components(mask, field.origin, field.dims, travel ? travel->cost : std::vector<uint32_t>(), min_size);
+  s.marked = marked;
+  return s;
+}
+
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {
   if (group_) throw std::runtime_error("TSDFGrid::RayCastSurface: not available on a sharded volume");
   SurfaceMaps m;

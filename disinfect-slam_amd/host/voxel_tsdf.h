@@ -104,6 +104,18 @@ class TSDFGrid {
   struct DistanceField ApplyFree(const FreeLayer& layer, const struct DistanceField& field,
                                  int64_t* promoted = nullptr);
 
+  // Frontiers and components (tsdf_frontier_mark / tsdf_components). Components: the 26-connected components
+  // of a mask over a box (nz * ny * nx bytes, members nonzero) as a FrontierSet whose mask is a copy; key
+  // (empty, or one uint32 per voxel) chooses each cluster's goal: the member with the least key. Frontiers: the
+  // mask of the field's observed-free voxels that touch unobserved space and, with travel, were reached by it,
+  // clustered with key = travel->cost, so a cluster's goal is its cheapest voxel to travel to. The field
+  // should come from ApplyFree and surface sites. Neither touches the volume. Not available on a sharded
+  // volume, like the distance field.
+  FrontierSet Components(const std::vector<uint8_t>& mask, const int32_t origin[3], const int32_t dims[3],
+                         const std::vector<uint32_t>& key = {}, int min_size = 1);
+  FrontierSet Frontiers(const struct DistanceField& field, const struct TravelField* travel = nullptr,
+                        int min_size = 1);
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

@@ -27,6 +27,10 @@ NUM_BUCKET = 1 << 21
 BLOCK_LEN = 8
 BLOCK_VOLUME = 512
 BLOCK_RECORD_BYTES = 16 + 12 * BLOCK_VOLUME  # TSDF_BLOCK_RECORD_BYTES: key header + block
+# tsdf_component, 64 bytes: a cluster of Engine.components / Engine.frontiers
+COMPONENT_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
+                            ("sum", "<i8", (3,)), ("goal", "<u4"), ("goal_key", "<u4")])
+TSDF_COMPONENT_NONE = 0xFFFFFFFF
 VOXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("tsdf", "<f4")])
 
 __all__ = [
@@ -1323,6 +1327,90 @@ class Engine:
         self._signal_torch(bits, st)
         _lib.check(rc, "tsdf_free_apply")
         return dict(field, state=st, promoted=int(n.value) if count else None)
+
+    # ---- frontiers and components ----
+    def frontier_mask(self, field, travel=None, device: bool = False, count: bool = True):
+        """The frontier of a distance field (tsdf_frontier_mark): mask 1 at every observed-free voxel
+        (state 1) that has an unobserved (state 0) face neighbour inside the box and, with `travel` (a
+        travel_field result over the same box), that the travel field reached. field should have been
+        promoted by free_apply and built from surface sites only (unknown=False). Returns dict(mask
+        (nz, ny, nx) uint8, marked: the number of ones (None with count=False, which keeps a device call
+        asynchronous), origin, dims): numpy, or with device=True a torch tensor on this engine's GPU. Does
+        not touch the volume: pending frames stay pending, and a shard engine serves as well."""
+        L = _lib.load()
+        if field.get("state") is None:
+            raise ValueError("frontier_mask: the field has no state (distance_field(..., state=True))")
+        o, d = [int(v) for v in field["origin"]], [int(v) for v in field["dims"]]
+        shape = (d[2], d[1], d[0])
+        if travel is not None and (tuple(int(v) for v in travel["dims"]) != tuple(d) or
+                                   tuple(int(v) for v in travel["origin"]) != tuple(o)):
+            raise ValueError("frontier_mask: the travel field's box is not the distance field's")
+        st = self._box_array(field["state"], np.uint8, shape, device, "state")
+        cost = None if travel is None else self._box_array(travel["cost"], np.uint32, shape, device, "cost")
+        if device:
+            import torch
+            mask = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+        else:
+            mask = np.empty(shape, np.uint8)
+        n = C.c_int64(0)
+        self._wait_torch(st, cost, mask)
+        rc = L.tsdf_frontier_mark(self._h, (C.c_int32 * 3)(*d), _ptr(st), _ptr(cost), _ptr(mask),
+                                  TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(n) if count else None)
+        self._signal_torch(st, cost, mask)
+        _lib.check(rc, "tsdf_frontier_mark")
+        return dict(mask=mask, marked=int(n.value) if count else None, origin=tuple(o), dims=tuple(d))
+
+    def components(self, mask, dims, key=None, min_size: int = 1, device: bool = False):
+        """The 26-connected components of a voxel mask over a box (tsdf_components). mask: (nz, ny, nx)
+        uint8, members nonzero; dims: (nx, ny, nz); key: optional uint32 array of the same shape (a travel
+        field's cost). Returns dict(label (nz, ny, nx) uint32: the least linear index (z * ny + y) * nx + x
+        among the members of the voxel's component, 0xFFFFFFFF off the mask; clusters: a numpy structured
+        array (COMPONENT_DTYPE: label, size, lo, hi, sum, goal, goal_key) of the components with size >=
+        min_size in ascending label -- goal the member with the least key, ties to the least index, label
+        without key; count = len(clusters); total: all components). label is numpy, or with device=True a
+        torch tensor on this engine's GPU. Does not touch the volume."""
+        L = _lib.load()
+        d = [int(v) for v in dims]
+        if len(d) != 3:
+            raise ValueError("dims are three integers")
+        ok = all(1 <= v <= 2048 for v in d) and d[0] * d[1] * d[2] <= 1 << 28
+        shape = (d[2], d[1], d[0]) if ok else tuple(np.shape(mask))
+        m = self._box_array(mask, np.uint8, shape, device, "mask")
+        k = None if key is None else self._box_array(key, np.uint32, shape, device, "key")
+        if device:
+            import torch
+            label = torch.empty(shape, dtype=torch.uint32, device=f"cuda:{self.device}")
+        else:
+            label = np.empty(shape, np.uint32)
+        c = _lib.ComponentsConfig()
+        L.tsdf_components_config_default(C.byref(c))
+        c.dims, c.min_size = (C.c_int32 * 3)(*d), int(min_size)
+        kind = TSDF_MEM_DEVICE if device else TSDF_MEM_HOST
+        count, total = C.c_int32(0), C.c_int32(0)
+        self._wait_torch(m, k, label)
+        # the two-call pattern with a first guess: a table too small asks again with the count it was told
+        cap = 4096
+        for attempt in range(2):
+            clusters = np.zeros(cap, COMPONENT_DTYPE)
+            rc = L.tsdf_components(self._h, C.byref(c), _ptr(m), _ptr(k), _ptr(label), kind, _ptr(clusters), cap,
+                                   C.byref(count), C.byref(total))
+            if rc != _lib.TSDF_ERR_CAPACITY:
+                break
+            cap = int(count.value)
+        self._signal_torch(m, k, label)
+        _lib.check(rc, "tsdf_components")
+        return dict(label=label, clusters=clusters[:count.value].copy(), count=int(count.value),
+                    total=int(total.value))
+
+    def frontiers(self, field, travel=None, min_size: int = 1, device: bool = False):
+        """Where the map ends, as clusters (frontier_mask, then components with key = travel["cost"]):
+        dict(mask, marked, label, clusters, count, total, origin, dims). A cluster's goal is then its
+        cheapest voxel to travel to and goal_key that cost (esdf.frontier_goals gives world positions and
+        metres, esdf.frontier_voxels a cluster's voxels)."""
+        fm = self.frontier_mask(field, travel, device=device)
+        cc = self.components(fm["mask"], fm["dims"], key=None if travel is None else travel["cost"],
+                             min_size=min_size, device=device)
+        return dict(fm, **cc)
 
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()

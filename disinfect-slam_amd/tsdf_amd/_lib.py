@@ -207,6 +207,19 @@ class FreeBox(C.Structure):
     _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3)]
 
 
+class ComponentsConfig(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("min_size", C.c_int32)]
+
+
+class Component(C.Structure):
+    """tsdf_component: 64 bytes."""
+    _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("sum", C.c_int64 * 3), ("goal", C.c_uint32), ("goal_key", C.c_uint32)]
+
+
+TSDF_COMPONENT_NONE = 0xFFFFFFFF
+
+
 EXPORTS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_integrate", "tsdf_raycast",
     "tsdf_query", "tsdf_extract_mesh", "tsdf_get_stats", "tsdf_synchronize", "tsdf_flush", "tsdf_profile_begin", "tsdf_profile_end",
@@ -234,6 +247,7 @@ EXPORTS = [
     "tsdf_uv_irradiance", "tsdf_uv_plan_config_default", "tsdf_uv_plan",
     "tsdf_travel_config_default", "tsdf_travel_field", "tsdf_travel_paths",
     "tsdf_free_words", "tsdf_free_observe", "tsdf_free_apply",
+    "tsdf_components_config_default", "tsdf_frontier_mark", "tsdf_components",
 ]
 
 _lib = None
@@ -339,6 +353,11 @@ def load(path: str | None = None):
                                     C.c_float]
     L.tsdf_free_apply.argtypes = [P, C.POINTER(FreeBox), P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, i,
                                   C.POINTER(C.c_int64)]
+    L.tsdf_components_config_default.argtypes = [C.POINTER(ComponentsConfig)]
+    L.tsdf_components_config_default.restype = None
+    L.tsdf_frontier_mark.argtypes = [P, C.POINTER(C.c_int32), P, P, P, i, C.POINTER(C.c_int64)]
+    L.tsdf_components.argtypes = [P, C.POINTER(ComponentsConfig), P, P, P, i, P, C.c_int32, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32)]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -388,7 +407,7 @@ def load(path: str | None = None):
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
                  "tsdf_point_map_normals", "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
                  "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths",
-                 "tsdf_free_observe", "tsdf_free_apply"):
+                 "tsdf_free_observe", "tsdf_free_apply", "tsdf_frontier_mark", "tsdf_components"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -157,3 +157,34 @@ def free_fraction(layer) -> float:
     """The fraction of the box's voxels observed free."""
     m = free_mask(layer)
     return float(m.sum()) / float(m.size)
+
+
+# ---- frontiers and components (Engine.frontiers / components; DESIGN.md "Frontiers and components") ----
+def _host(a) -> np.ndarray:
+    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+
+
+def frontier_goals(fr, voxel: float):
+    """World positions of the clusters of an Engine.frontiers result, voxel v at v * voxel: dict(goal (k, 3)
+    float32: each cluster's cheapest voxel to travel to, centroid (k, 3) float32: float32(sum / size + origin)
+    * voxel with the quotient in float64, metres (k,) float32: goal_key / 3 * voxel, the travel distance to
+    the goal (0 without a travel field, inf for a key of 0xFFFFFFFF))."""
+    c = fr["clusters"]
+    nx, ny, _ = (int(v) for v in fr["dims"])
+    o = np.asarray(fr["origin"], np.int64)
+    g = c["goal"].astype(np.int64)
+    v = np.stack([g % nx, g // nx % ny, g // (nx * ny)], -1).reshape(-1, 3) + o
+    goal = (v.astype(np.float32) * np.float32(voxel)).astype(np.float32)
+    mean = c["sum"].astype(np.float64).reshape(-1, 3) / np.maximum(c["size"], 1).astype(np.float64).reshape(-1, 1)
+    centroid = ((mean + o.astype(np.float64)).astype(np.float32) * np.float32(voxel)).astype(np.float32)
+    k = c["goal_key"]
+    m = (k.astype(np.float32) / np.float32(3)) * np.float32(voxel)
+    return dict(goal=goal, centroid=centroid, metres=np.where(k == UNREACHED, np.float32(np.inf), m).astype(np.float32))
+
+
+def frontier_voxels(fr, k: int) -> np.ndarray:
+    """The global voxels (m, 3) int64, x y z, of cluster k of an Engine.frontiers / components result (with
+    `origin`; box-local without), in ascending linear index."""
+    lab = _host(fr["label"])
+    z, y, x = np.nonzero(lab == np.uint32(fr["clusters"]["label"][k]))
+    return np.stack([x, y, z], -1).astype(np.int64) + np.asarray(fr.get("origin", (0, 0, 0)), np.int64)

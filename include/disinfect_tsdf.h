@@ -800,6 +800,72 @@ int tsdf_free_apply(tsdf_engine* e, const tsdf_free_box* box, const uint32_t* bi
                     const int32_t dims[3], uint8_t* state, int mem_kind /* bits and state alike */,
                     int64_t* promoted /* host, may be NULL */);
 
+/* ---- Frontiers and connected components over a box (no reference counterpart) ----
+ * Where the map ends, as a short list of places to look from. A frontier is an observed-free, reachable voxel
+ * that touches unobserved space; tsdf_components clusters any voxel mask into its 26-connected components and
+ * reports each one's size, place and cheapest member. All integers, so the results are exact. Boxes as
+ * everywhere: dims = (nx, ny, nz), each in 1 .. 2048, nx * ny * nz <= 2^28, arrays nz * ny * nx with x fastest,
+ * linear index (z * ny + y) * nx + x.
+ *
+ * tsdf_frontier_mark: mask[v] = 1 when all three hold, else 0:
+ *   state[v] == 1;  cost == NULL or cost[v] != TSDF_TRAVEL_UNREACHED;
+ *   at least one of the six face neighbours of v inside the box has state 0.
+ * Neighbours outside the box never count, as the travel field's steps do not: a box that is all state 1 has no
+ * frontier. *marked is the number of ones. state is a distance field's state and cost a travel field's cost
+ * over the same box. The distance field should use surface sites only (TSDF_EDT_SURFACE): with
+ * TSDF_EDT_UNKNOWN sites every passable voxel keeps its clearance from unobserved space, so no voxel next to
+ * unobserved space is reached and no frontier is marked. state should have been promoted by tsdf_free_apply:
+ * otherwise the whole outer skin of the thin observed shell around the surfaces is "frontier".
+ * state, cost and mask are mem_kind memory alike. Device memory: asynchronous on the engine stream when marked
+ * is NULL, one synchronisation otherwise (tsdf_free_apply's rule). Host memory: the call copies up, runs,
+ * copies down and synchronises. Required: e, dims, state and mask non-NULL, dims as above, mem_kind one of the
+ * two; anything else is TSDF_ERR_INVALID_ARG with nothing written.
+ *
+ * tsdf_components: members are the voxels with mask[v] != 0. Two members are adjacent when they are among
+ * each other's 26 neighbours inside the box (the travel field's steps); components are the classes of the
+ * transitive closure. label[v] is the least linear index among the members of v's component, and
+ * TSDF_COMPONENT_NONE for a voxel off the mask. The labelling is therefore unique: it does not depend on
+ * scheduling or on the order of any atomic. *total is the number of components, *count the number with
+ * size >= min_size, and clusters[0 .. *count) are those, in ascending label. goal is the member with the least
+ * key[v], ties to the least linear index, and goal_key its key -- with key a travel field's cost, the
+ * component's cheapest voxel to travel to, goal_key / 3 voxels away; key == NULL gives goal = label and
+ * goal_key = 0. lo, hi and sum are in box-local voxel coordinates; sum / size is the centroid.
+ * capacity == 0 (clusters may then be NULL) is the query form: labels and counts are written and the call
+ * returns TSDF_OK. *count > capacity > 0 writes labels and counts, nothing to clusters, and returns
+ * TSDF_ERR_CAPACITY. label is written in full on every accepted call. Required: e, cfg, mask, label and count
+ * non-NULL, dims as above, min_size >= 1, capacity >= 0, clusters non-NULL when capacity > 0, mem_kind one of
+ * the two; anything else is TSDF_ERR_INVALID_ARG with nothing written. mask, key and label are mem_kind
+ * memory alike; cfg, clusters, count and total are host memory. The call has synchronised the engine stream
+ * when it returns.
+ * Both calls leave the volume alone: the engine lends its stream and scratch (grown on demand, freed by
+ * tsdf_destroy: 4 bytes per voxel plus 576 per component for tsdf_components, 9 more per voxel for host
+ * arrays), no status bits are set, pending pipelined frames stay pending, and a shard engine
+ * (shard_count > 1) serves as well as any other. */
+#define TSDF_COMPONENT_NONE 0xFFFFFFFFu
+typedef struct tsdf_components_config {
+  int32_t dims[3];  /* nx, ny, nz of the box */
+  int32_t min_size; /* >= 1: clusters lists the components with at least this many voxels */
+} tsdf_components_config;
+typedef struct tsdf_component {
+  uint32_t label;    /* least linear index of the component */
+  uint32_t size;     /* voxels */
+  int32_t lo[3];     /* box-local bounding box, x y z, inclusive */
+  int32_t hi[3];
+  int64_t sum[3];    /* sums of the members' box-local x, y, z: centroid = sum / size */
+  uint32_t goal;     /* linear index of the member with the least key[v], ties to the least index; label when
+                        key is NULL */
+  uint32_t goal_key; /* key[goal]; 0 when key is NULL */
+} tsdf_component;
+/* min_size 1; dims zero */
+void tsdf_components_config_default(tsdf_components_config* cfg);
+int tsdf_frontier_mark(tsdf_engine* e, const int32_t dims[3], const uint8_t* state,
+                       const uint32_t* cost /* may be NULL */, uint8_t* mask, int mem_kind /* all three alike */,
+                       int64_t* marked /* host, may be NULL */);
+int tsdf_components(tsdf_engine* e, const tsdf_components_config* cfg, const uint8_t* mask,
+                    const uint32_t* key /* may be NULL */, uint32_t* label, int mem_kind /* all three alike */,
+                    tsdf_component* clusters /* host */, int32_t capacity, int32_t* count /* host */,
+                    int32_t* total /* host, may be NULL */);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
