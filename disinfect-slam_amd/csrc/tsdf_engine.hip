@@ -29,6 +29,7 @@ void set_error(const char* what) { g_last_error = what; }
 //   TSDF_CAND_CAP=n               (tests) smaller carve-candidate list, to exercise its overflow
 //   TSDF_MESH_GRID=n              (tests) fewer k_mesh workgroups, to exercise its grid stride
 //   TSDF_FREE_CULL=0              (A/B, tests) tsdf_free_observe without its two culls (full words, bricks outside the frustum)
+//   TSDF_VIEW_SKIP=0              (A/B, tests) tsdf_view_gain with the plain march (no ray / box cut) and no per-view brick cull
 // ---------------------------------------------------------------------------------------------
 static EnvKnobs read_env_knobs() {
   EnvKnobs k;
@@ -38,6 +39,7 @@ static EnvKnobs read_env_knobs() {
   };
   if (const char* v = std::getenv("TSDF_PIPELINE")) k.pipeline = v[0] != '0';
   if (const char* v = std::getenv("TSDF_FREE_CULL")) k.free_cull = v[0] != '0';
+  if (const char* v = std::getenv("TSDF_VIEW_SKIP")) k.view_skip = v[0] != '0';
   k.pipe_max_pixels = num("TSDF_PIPE_MAX_PIXELS", -1);
   k.frame_order = (int)std::max(-1ll, num("TSDF_FRAME_ORDER", -1));
   k.frame_upd_wgs = (int)num("TSDF_FRAME_UPD_WGS", 0);

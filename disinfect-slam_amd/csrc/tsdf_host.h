@@ -142,6 +142,7 @@ struct TraceRange {
 struct EnvKnobs {
   bool pipeline = true;
   bool free_cull = true;  // (beside `pipeline`, in its padding: the struct keeps its size)
+  bool view_skip = true;  // (likewise)
   int64_t pipe_max_pixels = -1;
   int frame_order = -1, frame_upd_wgs = 0, cand_cap = 0, mesh_grid = 0;
 };
@@ -316,6 +317,9 @@ struct tsdf_engine {
   // words, a slot per voxel, the host arrays' staging, then accumulators and records per component, one
   // section each. Grow-only. (Last, as fr_buf was.)
   DevBuf<uint8_t> cc_buf;
+  // view gain (tsdf_view_gain; tsdf_host_view.hip): the views, their gains, a batch's pixel records and, for
+  // host arrays, their staging, one section each. Grow-only. (Last, as cc_buf was.)
+  DevBuf<uint8_t> vw_buf;
 
   tsdf_engine() = default;
   // D's buffers, the pinned mirrors, events and streams; the scratch above frees itself. The caller has

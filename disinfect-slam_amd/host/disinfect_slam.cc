@@ -87,6 +87,19 @@ FrontierSet DISINFSystem::query_frontiers(const DistanceField& field, const Trav
   return TSDF_->Frontiers(field, travel, min_size);
 }
 
+NextViews DISINFSystem::query_next_views(int k, const BoundingCube<float>& volumn, const std::vector<float>& from_world,
+                                         const CameraParams& cam, float far, float clearance_m, int min_size, int yaws,
+                                         float pitch, int max_dist) {
+  const DistanceField field = query_free_space(query_distance_field(volumn, max_dist));
+  const TravelField travel = query_travel_field(field, from_world, clearance_m, false);
+  const FrontierSet fs = query_frontiers(field, &travel, min_size);
+  std::vector<int32_t> owner;
+  const std::vector<SE3<float>> views = view_candidates(fs.clusters, fs.origin, fs.dims, TSDF_->voxel_size(), yaws, pitch, &owner);
+  NextViews out = TSDF_->NextViewsOf(field, views, cam, k, far);
+  out.cluster = owner;
+  return out;
+}
+
 void DISINFSystem::irradiate(TriMesh& mesh, const std::vector<UVEmitter>& emitters, const tsdf_uv_config* cfg) {
   const size_t nv = mesh.verts.size() / 3;
   if (mesh.normals.empty()) mesh.normals = TSDF_->SurfaceNormals(mesh.verts, 0.5f);

@@ -86,6 +86,14 @@ class DISINFSystem {
   // its goal: the member cheapest to travel to, goal_key / 3 voxels away (frontier_goals in uv_dose.h gives
   // world positions). field should come from query_free_space, over surface sites.
   FrontierSet query_frontiers(const DistanceField& field, const TravelField* travel = nullptr, int min_size = 1);
+  // Where to look next (DESIGN.md "View gain"): the distance field over `volumn` (surface sites), promoted by
+  // the free layer (enable_free_space first), the travel field from from_world with clearance_m, its frontiers of
+  // at least min_size voxels, `yaws` candidate poses of camera `cam` at every cluster's goal (view_candidates in
+  // uv_dose.h), and the greedy choice of up to k of them by the unobserved voxels each would add
+  // (TSDFSystem::NextViewsOf), rays marched `far` metres.
+  NextViews query_next_views(int k, const BoundingCube<float>& volumn, const std::vector<float>& from_world,
+                             const CameraParams& cam, float far = 3.0f, float clearance_m = 0.0f, int min_size = 1,
+                             int yaws = 8, float pitch = 0.0f, int max_dist = 255);
   TSDFSystem& tsdf() { return *TSDF_; }
 
  private:

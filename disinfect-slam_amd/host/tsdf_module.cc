@@ -169,6 +169,43 @@ FrontierSet TSDFSystem::Components(const std::vector<uint8_t>& mask, const int32
   return tsdf_.Components(mask, origin, dims, key, min_size);
 }
 
+ViewGainResult TSDFSystem::ViewGain(const struct DistanceField& field, const std::vector<SE3<float>>& views,
+                                    const CameraParams& cam, float far, float step, float margin, float miss_depth,
+                                    const FreeLayer* seen, bool want_depth) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  return tsdf_.ViewGain(field, views, cam, far, step, margin, miss_depth, seen, want_depth);
+}
+
+NextViews TSDFSystem::NextViewsOf(const struct DistanceField& field, const std::vector<SE3<float>>& views,
+                                  const CameraParams& cam, int k, float far, float step, float miss_depth) {
+  std::unique_lock<std::mutex> lock(mtx_queue_);
+  cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });
+  std::lock_guard<std::mutex> lr(mtx_read_);
+  NextViews out;
+  out.views = views;
+  for (int a = 0; a < 3; ++a) out.seen.origin[a] = field.origin[a], out.seen.dims[a] = field.dims[a];
+  const int64_t words = tsdf_free_words(field.dims);
+  if (words == 0) throw std::invalid_argument("TSDFSystem::NextViewsOf: the field's box is not a layer's");
+  out.seen.bits.assign((size_t)words, 0u);
+  std::vector<float> depth;  // (the images depend on the state alone: one march serves every round)
+  const size_t npix = (size_t)std::max(cam.img_w, 0) * (size_t)std::max(cam.img_h, 0);
+  for (int round = 0; round < k && !views.empty(); ++round) {
+    ViewGainResult r = tsdf_.ViewGain(field, views, cam, far, step, -1.0f, miss_depth, &out.seen, depth.empty());
+    if (depth.empty()) depth.swap(r.depth);
+    size_t best = 0;
+    for (size_t i = 1; i < r.gain.size(); ++i)
+      if (r.gain[i] > r.gain[best]) best = i;  // (the first of the largest)
+    if (r.gain[best] <= 0) break;
+    const Mat img(cam.img_h, cam.img_w, CV_32FC1, depth.data() + best * npix);
+    tsdf_.ObserveFree(out.seen, img, 2.0f * far, cam.intrinsics, views[best]);
+    out.chosen.push_back((int32_t)best);
+    out.gains.push_back(r.gain[best]);
+  }
+  return out;
+}
+
 void TSDFSystem::EnableFreeSpace(const BoundingCube<float>& volumn) {
   std::unique_lock<std::mutex> lock(mtx_queue_);
   cv_idle_.wait(lock, [&] { return inputs_.empty() && !busy_; });

@@ -95,6 +95,15 @@ class TSDFSystem {
                         int min_size = 1);
   FrontierSet Components(const std::vector<uint8_t>& mask, const int32_t origin[3], const int32_t dims[3],
                          const std::vector<uint32_t>& key = {}, int min_size = 1);
+  // view gain (TSDFGrid::ViewGain), after every queued frame; NextViews: the greedy choice of up to k of
+  // `views` -- each round the largest gain against what the chosen views will observe wins (ties to the lowest
+  // index, stop at gain 0) and its predicted image is committed with ObserveFree (max_depth 2 far; the margin is
+  // the truncation, so a gain is exactly what the commit adds)
+  ViewGainResult ViewGain(const struct DistanceField& field, const std::vector<SE3<float>>& views, const CameraParams& cam,
+                          float far, float step = 0.0f, float margin = -1.0f, float miss_depth = -1.0f,
+                          const FreeLayer* seen = nullptr, bool want_depth = false);
+  NextViews NextViewsOf(const struct DistanceField& field, const std::vector<SE3<float>>& views, const CameraParams& cam,
+                        int k, float far, float step = 0.0f, float miss_depth = -1.0f);
   // Observed free space (TSDFGrid::ObserveFree / ApplyFree). EnableFreeSpace: from the next queued frame on,
   // the worker also observes every frame it integrates into a layer over `volumn` that the system owns (a raw
   // frame's half-size depth is taken from HalfRGBD once more); calling it again starts a cleared layer.

@@ -306,6 +306,23 @@ struct FreeLayer {
   }
 };
 
+// What candidate camera poses would observe (tsdf_view_gain): gain[i] the unobserved voxels of the box that view
+// i's predicted depth image marks free, depth the predicted images (views x rows x cols; empty unless asked for).
+struct ViewGainResult {
+  int rows = 0, cols = 0;
+  std::vector<int64_t> gain;
+  std::vector<float> depth;
+};
+// The greedy choice of next views (DISINFSystem::query_next_views): the candidates and the cluster each belongs
+// to, the chosen candidates in order with the gain each added, and the layer of what they will observe.
+struct NextViews {
+  std::vector<SE3<float>> views;
+  std::vector<int32_t> cluster;
+  std::vector<int32_t> chosen;
+  std::vector<int64_t> gains;
+  FreeLayer seen;
+};
+
 // The pose of a depth frame against the volume (tsdf_track). degenerate: too few correspondences
 // or singular normal equations; pose is then the last good estimate (the guess when none was made).
 struct TrackResult {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "disinfect_tsdf.h"
+#include "tsdf_types.h"
 
 namespace disinfect {
 
@@ -223,6 +224,84 @@ std::vector<float> frontier_goals(const std::vector<Cluster>& clusters, const in
     const double size = (double)(c.size > 0 ? c.size : 1u);
     for (int a = 0; a < 3; ++a) out.push_back((float)((double)c.sum[a] / size + (double)origin[a]) * voxel);
     out.push_back(c.goal_key == TSDF_TRAVEL_UNREACHED ? INFINITY : ((float)c.goal_key / 3.0f) * voxel);
+  }
+  return out;
+}
+
+// ---- view gain (tsdf_types.h ViewGainResult / NextViews; tsdf_amd.esdf.look_at / view_candidates) ----
+// cam_T_world of a camera at `eye` looking at `target`: z forward, x right, y down, x horizontal with respect to
+// `up`. An `up` (anti)parallel to the viewing direction is replaced by the world x axis, or the y axis when the
+// camera looks along x. Double throughout, one operation at a time in the order of esdf.look_at, then rounded
+// to float: the two agree bit for bit.
+inline SE3<float> look_at_pose(const double eye[3], const double target[3], const double up_in[3] = nullptr) {
+  const double up0[3] = {0.0, 0.0, 1.0};
+  const double* up = up_in ? up_in : up0;
+  double f[3] = {target[0] - eye[0], target[1] - eye[1], target[2] - eye[2]};
+  double n = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+  if (!(n > 0.0 && std::isfinite(n))) throw std::invalid_argument("look_at_pose: eye and target coincide (or are not finite)");
+  for (int a = 0; a < 3; ++a) f[a] = f[a] / n;
+  auto cross = [](const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  double r[3], d[3];
+  cross(f, up, r);
+  n = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  if (!(n > 1e-9)) {
+    const double ex[3] = {1.0, 0.0, 0.0}, ey[3] = {0.0, 1.0, 0.0};
+    cross(f, std::fabs(f[0]) < 0.9 ? ex : ey, r);
+    n = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  }
+  for (int a = 0; a < 3; ++a) r[a] = r[a] / n;
+  cross(f, r, d);
+  // cam_R_world: rows right, down, forward; its quaternion by the largest of w, x, y, z (Shepperd)
+  const double* m[3] = {r, d, f};
+  const double tr = m[0][0] + m[1][1] + m[2][2];
+  double q[4], s;
+  if (tr > 0.0) {
+    s = std::sqrt(tr + 1.0) * 2.0;
+    q[0] = (m[2][1] - m[1][2]) / s, q[1] = (m[0][2] - m[2][0]) / s, q[2] = (m[1][0] - m[0][1]) / s, q[3] = 0.25 * s;
+  } else if (m[0][0] > m[1][1] && m[0][0] > m[2][2]) {
+    s = std::sqrt(1.0 + m[0][0] - m[1][1] - m[2][2]) * 2.0;
+    q[0] = 0.25 * s, q[1] = (m[0][1] + m[1][0]) / s, q[2] = (m[0][2] + m[2][0]) / s, q[3] = (m[2][1] - m[1][2]) / s;
+  } else if (m[1][1] > m[2][2]) {
+    s = std::sqrt(1.0 + m[1][1] - m[0][0] - m[2][2]) * 2.0;
+    q[0] = (m[0][1] + m[1][0]) / s, q[1] = 0.25 * s, q[2] = (m[1][2] + m[2][1]) / s, q[3] = (m[0][2] - m[2][0]) / s;
+  } else {
+    s = std::sqrt(1.0 + m[2][2] - m[0][0] - m[1][1]) * 2.0;
+    q[0] = (m[0][2] + m[2][0]) / s, q[1] = (m[1][2] + m[2][1]) / s, q[2] = 0.25 * s, q[3] = (m[1][0] - m[0][1]) / s;
+  }
+  if (q[3] < 0.0)
+    for (int a = 0; a < 4; ++a) q[a] = -q[a];
+  double t[3];
+  for (int a = 0; a < 3; ++a) t[a] = -(m[a][0] * eye[0] + m[a][1] * eye[1] + m[a][2] * eye[2]);
+  return SE3<float>((float)q[0], (float)q[1], (float)q[2], (float)q[3], (float)t[0], (float)t[1], (float)t[2]);
+}
+
+// Candidate camera poses for a frontier set: at every cluster's goal (frontier_goals), `yaws` poses turned about
+// the world z axis, yaw 2 pi k / yaws from the world x axis, looking `pitch` radians above the horizon;
+// cluster-major. owner (may be null) receives the index of the cluster each pose belongs to.
+template <typename Cluster>
+std::vector<SE3<float>> view_candidates(const std::vector<Cluster>& clusters, const int32_t origin[3],
+                                        const int32_t dims[3], float voxel, int yaws = 8, float pitch = 0.0f,
+                                        std::vector<int32_t>* owner = nullptr) {
+  if (yaws < 1) throw std::invalid_argument("view_candidates: yaws >= 1");
+  const std::vector<float> goals = frontier_goals(clusters, origin, dims, voxel);
+  std::vector<SE3<float>> out;
+  out.reserve(clusters.size() * (size_t)yaws);
+  if (owner) owner->clear();
+  const double pi = 3.141592653589793;
+  for (size_t c = 0; c < clusters.size(); ++c) {
+    const double e[3] = {(double)goals[7 * c], (double)goals[7 * c + 1], (double)goals[7 * c + 2]};
+    for (int k = 0; k < yaws; ++k) {
+      const double a = 2.0 * pi * (double)k / (double)yaws;
+      const double dirn[3] = {std::cos(a) * std::cos((double)pitch), std::sin(a) * std::cos((double)pitch),
+                              std::sin((double)pitch)};
+      const double t[3] = {e[0] + dirn[0], e[1] + dirn[1], e[2] + dirn[2]};
+      out.push_back(look_at_pose(e, t));
+      if (owner) owner->push_back((int32_t)c);
+    }
   }
   return out;
 }

@@ -436,6 +436,44 @@ FrontierSet TSDFGrid::Frontiers(const struct DistanceField& field, const struct 
   return s;
 }
 
+ViewGainResult TSDFGrid::ViewGain(const struct DistanceField& field, const std::vector<SE3<float>>& views,
+                                  const CameraParams& cam, float far, float step, float margin, float miss_depth,
+                                  const FreeLayer* seen, bool want_depth) {
+  if (group_) throw std::runtime_error("TSDFGrid::ViewGain: not available on a sharded volume");
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) n *= (size_t)std::max(field.dims[a], 0);
+  if (n == 0 || field.state.size() != n)
+    throw std::invalid_argument("TSDFGrid::ViewGain: the field needs a state for every voxel of its box");
+  if (seen) {
+    for (int a = 0; a < 3; ++a)
+      if (seen->origin[a] != field.origin[a] || seen->dims[a] != field.dims[a])
+        throw std::invalid_argument("TSDFGrid::ViewGain: the seen layer's box is not the field's");
+    if ((int64_t)seen->bits.size() != tsdf_free_words(seen->dims) || seen->bits.empty())
+      throw std::invalid_argument("TSDFGrid::ViewGain: the layer's words do not match its box");
+  }
+  tsdf_view_config c;
+  tsdf_view_config_default(engine_, &c);
+  for (int a = 0; a < 3; ++a) c.origin[a] = field.origin[a], c.dims[a] = field.dims[a];
+  c.width = cam.img_w, c.height = cam.img_h;
+  c.K = tsdf_intrinsics{cam.intrinsics.fx, cam.intrinsics.fy, cam.intrinsics.cx, cam.intrinsics.cy};
+  c.far = far;
+  if (step > 0.0f) c.step = step;
+  if (margin >= 0.0f) c.margin = margin;
+  c.miss_depth = miss_depth < 0.0f ? far : miss_depth;
+  ViewGainResult r;
+  r.rows = cam.img_h, r.cols = cam.img_w;
+  r.gain.assign(views.size(), 0);
+  std::vector<tsdf_pose> poses;
+  poses.reserve(views.size());
+  for (const SE3<float>& v : views) poses.push_back(to_pose(v));
+  if (want_depth) r.depth.resize(views.size() * (size_t)std::max(cam.img_w, 0) * (size_t)std::max(cam.img_h, 0));
+  check_tsdf(tsdf_view_gain(engine_, &c, field.state.data(), seen ? seen->bits.data() : nullptr, poses.data(),
+                            (int32_t)views.size(), r.gain.data(), want_depth && !r.depth.empty() ? r.depth.data() : nullptr,
+                            TSDF_MEM_HOST),
+             "tsdf_view_gain");
+  return r;
+}
+
 SurfaceMaps TSDFGrid::RayCastSurface(float max_depth, const CameraParams& cam, const SE3<float>& cam_T_world) {
   if (group_) throw std::runtime_error("TSDFGrid::RayCastSurface: not available on a sharded volume");
   SurfaceMaps m;

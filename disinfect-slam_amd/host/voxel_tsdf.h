@@ -116,6 +116,15 @@ class TSDFGrid {
   FrontierSet Frontiers(const struct DistanceField& field, const struct TravelField* travel = nullptr,
                         int min_size = 1);
 
+  // View gain (tsdf_view_gain): for each candidate cam_T_world, the unobserved voxels (state 0) of the field's
+  // box, outside `seen` when given (a layer over the same box), that the view's predicted depth image would mark
+  // free. Rays are marched `far` metres in steps of `step` (<= 0: the voxel size) to the first state-2 voxel;
+  // a ray that meets none reads miss_depth (< 0: far; 0: no return). margin < 0: the truncation. Host arrays;
+  // does not touch the volume. Not available on a sharded volume, like the distance field.
+  ViewGainResult ViewGain(const struct DistanceField& field, const std::vector<SE3<float>>& views,
+                          const CameraParams& cam, float far, float step = 0.0f, float margin = -1.0f,
+                          float miss_depth = -1.0f, const FreeLayer* seen = nullptr, bool want_depth = false);
+
   // what RayCast sees as float maps (tsdf_raycast_surface). Not available on a sharded volume:
   // throws std::runtime_error, like Track and HalfRGBD.
   SurfaceMaps RayCastSurface(float max_depth, const CameraParams& virtual_cam, const SE3<float>& cam_T_world);

@@ -31,6 +31,8 @@ BLOCK_RECORD_BYTES = 16 + 12 * BLOCK_VOLUME  # TSDF_BLOCK_RECORD_BYTES: key head
 COMPONENT_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
                             ("sum", "<i8", (3,)), ("goal", "<u4"), ("goal_key", "<u4")])
 TSDF_COMPONENT_NONE = 0xFFFFFFFF
+# Engine.view_gain takes its views this many at a time (TSDF_VIEW_BATCH), fewer while a batch's pixels exceed 2^22
+VIEW_BATCH = 64
 VOXEL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("tsdf", "<f4")])
 
 __all__ = [
@@ -1411,6 +1413,80 @@ class Engine:
         cc = self.components(fm["mask"], fm["dims"], key=None if travel is None else travel["cost"],
                              min_size=min_size, device=device)
         return dict(fm, **cc)
+
+    # ---- view gain ----
+    def view_gain(self, field_or_state, views, K, width: int, height: int, far: float, step=None, margin=None,
+                  miss_depth=None, seen=None, depth: bool = False, device: bool = False):
+        """The unobserved voxels each candidate camera pose would observe (tsdf_view_gain). field_or_state:
+        a distance_field / free_apply result (dict with state, origin, dims) or a tuple (state, origin, dims),
+        state (nz, ny, nx) uint8; views: a list of SE3 (cam_T_world); K: the views' intrinsics. Each view's
+        depth image is predicted by marching its rays `far` metres in steps of `step` (default: the voxel
+        size) to the first state-2 voxel -- miss_depth (default far; 0: no return) where there is none --
+        and gain[i] counts the state-0 voxels, outside the layer `seen` (esdf.free_layer over the same box)
+        when given, that free_observe would mark from that image with truncation `margin` (default: the
+        engine's). Returns dict(gain (V,) int64, depth (V, H, W) float32 or None, origin, dims): numpy, or
+        with device=True the depth a torch tensor on this engine's GPU (state and seen are uploaded when
+        they are host arrays). Does not touch the volume: pending frames stay pending, and a shard engine
+        serves as well."""
+        L = _lib.load()
+        if isinstance(field_or_state, dict):
+            if field_or_state.get("state") is None:
+                raise ValueError("view_gain: the field has no state (distance_field(..., state=True))")
+            state, origin, dims = field_or_state["state"], field_or_state["origin"], field_or_state["dims"]
+        else:
+            state, origin, dims = field_or_state
+        o, d = [int(v) for v in origin], [int(v) for v in dims]
+        if len(o) != 3 or len(d) != 3:
+            raise ValueError("view_gain: origin and dims are three integers each")
+        st = self._box_array(state, np.uint8, (d[2], d[1], d[0]), device, "state")
+        bits = None
+        if seen is not None:
+            if tuple(int(v) for v in seen["dims"]) != tuple(d) or tuple(int(v) for v in seen["origin"]) != tuple(o):
+                raise ValueError("view_gain: the seen layer's box is not the state's")
+            bits = seen["bits"]
+            wshape = (d[2], d[1], (d[0] + 31) // 32)
+            if device:
+                import torch
+                if not _is_torch_cuda(bits):
+                    bits = torch.as_tensor(np.ascontiguousarray(bits, dtype=np.uint32).view(np.int32),
+                                           device=f"cuda:{self.device}")
+                if bits.dtype != torch.int32:
+                    raise ValueError("view_gain: a device layer's bits are torch.int32")
+                bits = bits.contiguous()
+            else:
+                bits = bits.cpu().numpy().view(np.uint32) if _is_torch_cuda(bits) else bits
+                bits = np.ascontiguousarray(bits, dtype=np.uint32)
+            if tuple(bits.shape) != wshape:
+                raise ValueError(f"view_gain: seen bits: expected shape {wshape}, got {tuple(bits.shape)}")
+        views = list(views)
+        nv, w, h = len(views), int(width), int(height)
+        c = _lib.ViewConfig()
+        L.tsdf_view_config_default(self._h, C.byref(c))
+        c.origin, c.dims = (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d)
+        c.width, c.height = w, h
+        c.K = K._c() if isinstance(K, CameraIntrinsics) else _lib.Intrinsics(*[float(v) for v in K])
+        c.far = float(far)
+        c.miss_depth = float(far) if miss_depth is None else float(miss_depth)
+        if step is not None:
+            c.step = float(step)
+        if margin is not None:
+            c.margin = float(margin)
+        poses = (_lib.Pose * max(nv, 1))(*[v._c() for v in views])
+        gain = np.zeros(nv, np.int64)
+        out = None
+        if depth:
+            shape = (nv, max(h, 0), max(w, 0))
+            if device:
+                import torch
+                out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}")
+            else:
+                out = np.empty(shape, np.float32)
+        self._wait_torch(st, bits, out)
+        rc = L.tsdf_view_gain(self._h, C.byref(c), _ptr(st), _ptr(bits), C.cast(poses, C.c_void_p), nv, _ptr(gain),
+                              _ptr(out) if nv else None, TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
+        self._signal_torch(st, bits, out)
+        _lib.check(rc, "tsdf_view_gain")
+        return dict(gain=gain, depth=out, origin=tuple(o), dims=tuple(d))
 
     def query(self, bounds=None) -> np.ndarray:
         L = _lib.load()

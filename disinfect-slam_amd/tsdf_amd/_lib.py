@@ -211,6 +211,12 @@ class ComponentsConfig(C.Structure):
     _fields_ = [("dims", C.c_int32 * 3), ("min_size", C.c_int32)]
 
 
+class ViewConfig(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("width", C.c_int32), ("height", C.c_int32),
+                ("K", Intrinsics), ("far", C.c_float), ("step", C.c_float), ("margin", C.c_float),
+                ("miss_depth", C.c_float)]
+
+
 class Component(C.Structure):
     """tsdf_component: 64 bytes."""
     _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
@@ -248,6 +254,7 @@ EXPORTS = [
     "tsdf_travel_config_default", "tsdf_travel_field", "tsdf_travel_paths",
     "tsdf_free_words", "tsdf_free_observe", "tsdf_free_apply",
     "tsdf_components_config_default", "tsdf_frontier_mark", "tsdf_components",
+    "tsdf_view_config_default", "tsdf_view_gain",
 ]
 
 _lib = None
@@ -358,6 +365,9 @@ def load(path: str | None = None):
     L.tsdf_frontier_mark.argtypes = [P, C.POINTER(C.c_int32), P, P, P, i, C.POINTER(C.c_int64)]
     L.tsdf_components.argtypes = [P, C.POINTER(ComponentsConfig), P, P, P, i, P, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32)]
+    L.tsdf_view_config_default.argtypes = [P, C.POINTER(ViewConfig)]
+    L.tsdf_view_config_default.restype = None
+    L.tsdf_view_gain.argtypes = [P, C.POINTER(ViewConfig), P, P, P, C.c_int32, P, P, i]
     L.tsdf_get_stats.argtypes = [P, C.POINTER(Stats), i]
     L.tsdf_synchronize.argtypes = [P]
     L.tsdf_flush.argtypes = [P]
@@ -407,7 +417,8 @@ def load(path: str | None = None):
                  "tsdf_extract_mesh_indexed", "tsdf_raycast_surface", "tsdf_icp_linearize", "tsdf_track",
                  "tsdf_point_map_normals", "tsdf_surface_normals", "tsdf_uv_dose", "tsdf_distance_field",
                  "tsdf_uv_irradiance", "tsdf_uv_plan", "tsdf_travel_field", "tsdf_travel_paths",
-                 "tsdf_free_observe", "tsdf_free_apply", "tsdf_frontier_mark", "tsdf_components"):
+                 "tsdf_free_observe", "tsdf_free_apply", "tsdf_frontier_mark", "tsdf_components",
+                 "tsdf_view_gain"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -188,3 +188,99 @@ def frontier_voxels(fr, k: int) -> np.ndarray:
     lab = _host(fr["label"])
     z, y, x = np.nonzero(lab == np.uint32(fr["clusters"]["label"][k]))
     return np.stack([x, y, z], -1).astype(np.int64) + np.asarray(fr.get("origin", (0, 0, 0)), np.int64)
+
+
+# ---- view gain (Engine.view_gain; DESIGN.md "View gain") ----
+def look_at(eye, target, up=(0.0, 0.0, 1.0)):
+    """cam_T_world (SE3) of a camera at `eye` looking at `target`: z forward, x right, y down, x horizontal with
+    respect to `up`. An `up` (anti)parallel to the viewing direction is replaced by the world x axis, or the y
+    axis when the camera looks along x. Float64 throughout, one operation at a time in the order of
+    host/uv_dose.h look_at_pose, then rounded to float32: the two agree bit for bit."""
+    import math
+    from . import SE3
+    e, t, u = ([float(np.float64(v)) for v in a] for a in (eye, target, up))
+    f = [t[0] - e[0], t[1] - e[1], t[2] - e[2]]
+    n = math.sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2])
+    if not (n > 0.0 and math.isfinite(n)):
+        raise ValueError("look_at: eye and target coincide (or are not finite)")
+    f = [f[0] / n, f[1] / n, f[2] / n]
+
+    def cross(a, b):
+        return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+    r = cross(f, u)
+    n = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    if not n > 1e-9:
+        r = cross(f, [1.0, 0.0, 0.0] if abs(f[0]) < 0.9 else [0.0, 1.0, 0.0])
+        n = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    r = [r[0] / n, r[1] / n, r[2] / n]
+    d = cross(f, r)
+    # cam_R_world: rows right, down, forward; its quaternion by the largest of w, x, y, z (Shepperd)
+    m = [r, d, f]
+    tr = m[0][0] + m[1][1] + m[2][2]
+    if tr > 0.0:
+        s = math.sqrt(tr + 1.0) * 2.0
+        q = [(m[2][1] - m[1][2]) / s, (m[0][2] - m[2][0]) / s, (m[1][0] - m[0][1]) / s, 0.25 * s]
+    elif m[0][0] > m[1][1] and m[0][0] > m[2][2]:
+        s = math.sqrt(1.0 + m[0][0] - m[1][1] - m[2][2]) * 2.0
+        q = [0.25 * s, (m[0][1] + m[1][0]) / s, (m[0][2] + m[2][0]) / s, (m[2][1] - m[1][2]) / s]
+    elif m[1][1] > m[2][2]:
+        s = math.sqrt(1.0 + m[1][1] - m[0][0] - m[2][2]) * 2.0
+        q = [(m[0][1] + m[1][0]) / s, 0.25 * s, (m[1][2] + m[2][1]) / s, (m[0][2] - m[2][0]) / s]
+    else:
+        s = math.sqrt(1.0 + m[2][2] - m[0][0] - m[1][1]) * 2.0
+        q = [(m[0][2] + m[2][0]) / s, (m[1][2] + m[2][1]) / s, 0.25 * s, (m[1][0] - m[0][1]) / s]
+    if q[3] < 0.0:
+        q = [-q[0], -q[1], -q[2], -q[3]]
+    tt = [-(m[a][0] * e[0] + m[a][1] * e[1] + m[a][2] * e[2]) for a in range(3)]
+    return SE3(np.array(q, np.float64).astype(np.float32), np.array(tt, np.float64).astype(np.float32))
+
+
+def view_candidates(fr, voxel: float, yaws: int = 8, pitch: float = 0.0):
+    """Candidate camera poses for an Engine.frontiers result: at every cluster's goal (frontier_goals: its
+    cheapest voxel to travel to), `yaws` poses turned about the world z axis, yaw 2 pi k / yaws from the world
+    x axis, looking `pitch` radians above the horizon. Returns (views: list of SE3 cam_T_world, cluster (n,)
+    int32: the index of the cluster each pose belongs to), cluster-major."""
+    import math
+    if yaws < 1:
+        raise ValueError("view_candidates: yaws >= 1")
+    goal = frontier_goals(fr, voxel)["goal"]
+    pitch = float(np.float32(pitch))  # (a float, as host/uv_dose.h view_candidates takes it)
+    views, owner = [], []
+    for c in range(goal.shape[0]):
+        e = [float(v) for v in goal[c]]
+        for k in range(yaws):
+            a = 2.0 * math.pi * float(k) / float(yaws)
+            dirn = [math.cos(a) * math.cos(pitch), math.sin(a) * math.cos(pitch), math.sin(pitch)]
+            views.append(look_at(e, [e[0] + dirn[0], e[1] + dirn[1], e[2] + dirn[2]]))
+            owner.append(c)
+    return views, np.asarray(owner, np.int32)
+
+
+def next_views(engine, field, views, K, width: int, height: int, k: int, far: float = 3.0, step=None,
+               miss_depth=None, seen=None, device: bool = False):
+    """The greedy choice of up to k next views: each round Engine.view_gain scores every view against the
+    layer `seen` (what the views chosen so far will observe; a cleared esdf.free_layer over the field's box
+    when None), the largest gain wins (ties to the lowest index), and the winner's predicted depth image is
+    committed into `seen` with Engine.free_observe (max_depth 2 far). Stops at gain 0. The margin is the
+    engine's truncation, so each gain is exactly the number of unobserved voxels the commit adds. Returns
+    (chosen: list of view indices, gains: list of int, seen)."""
+    views = list(views)
+    if seen is None:
+        seen = free_layer(field["origin"], field["dims"], device=(f"cuda:{engine.device}" if device else False))
+    chosen, gains, depth = [], [], None
+    for _ in range(max(int(k), 0)):
+        if not views:
+            break
+        r = engine.view_gain(field, views, K, width, height, far, step=step, miss_depth=miss_depth, seen=seen,
+                             depth=depth is None, device=device)
+        if depth is None:  # (the images depend on the state alone: one march serves every round)
+            depth = r["depth"]
+        g = r["gain"]
+        i = int(np.argmax(g))  # (the first of the largest)
+        if int(g[i]) <= 0:
+            break
+        engine.free_observe(seen, depth[i], K, views[i], 2.0 * float(far))
+        chosen.append(i)
+        gains.append(int(g[i]))
+    return chosen, gains, seen

@@ -866,6 +866,68 @@ int tsdf_components(tsdf_engine* e, const tsdf_components_config* cfg, const uin
                     tsdf_component* clusters /* host */, int32_t capacity, int32_t* count /* host */,
                     int32_t* total /* host, may be NULL */);
 
+/* ---- View gain: the unobserved voxels a candidate camera pose would observe (no reference counterpart) ----
+ * Frontier clusters say where to look from; this says what a pose there would show. For V candidate poses over
+ * the box of a distance field's state array, tsdf_view_gain predicts each pose's depth image from the state
+ * and counts the unobserved voxels (state 0) that image would mark free by tsdf_free_observe's own test. All
+ * integers and single float32 operations, one IEEE operation at a time with no contraction: the results are
+ * exact, and do not depend on scheduling, batching or TSDF_VIEW_SKIP (an A/B and test knob read at
+ * tsdf_create: 0 selects the plain march and disables the per-view brick cull).
+ *
+ * Predicted depth of view i (cam_T_world = views[i]) at pixel (u, v):
+ *   dc = (ifx u + icx 1, ify v + icy 1, 1) with ifx = 1 / fx, icx = -cx ifx (y likewise): the free test's ray
+ *   range = sqrt(dc.x dc.x + (dc.y dc.y + 1 1))
+ *   world_T_cam = SE3::Inverse of cam_T_world in host float order (n2 = (qx qx + qz qz) + (qy qy + qw qw),
+ *                 q' = (-qx, -qy, -qz, qw) / n2 or zero when n2 is not positive, t' = q' * (-t))
+ *   J = f2i(far / step), required in 1 .. 65536
+ *   for j = 1 .. J:  z_j = (float)j * step;  pc_j = (dc.x z_j, dc.y z_j, z_j);  pw_j = world_T_cam * pc_j;
+ *                    g_j = round(pw_j / voxel_size) per component, half away from zero, saturating, NaN -> 0
+ *   pred[i][v W + u] = z_j of the first j with g_j inside the box and state[g_j] == 2, else miss_depth.
+ * Every sample is a product and a transform of j, never a running sum. A sample outside the box is
+ * transparent (the camera may stand outside the box), and so are states 0 and 1 and every byte other than 2.
+ * depth_out, when non-NULL, receives pred (V x H x W).
+ *
+ * Gain: vis(g, i) is tsdf_free_observe's free(g, frame) with depth = pred[i], valid reduced to d != 0 (no
+ * max_depth test: (float)J * step may round above far) and truncation replaced by margin; the projection, the
+ * rounding, sdf = range (d - hz) >= margin and hz > 0 stay.
+ *   gain[i] = #{ g in the box : state[g] == 0 && !seen(g) && vis(g, i) }
+ * seen is a free layer over the same box (tsdf_free_words layout; NULL: none; padding bits are ignored): the
+ * voxels that views already chosen will observe. To commit view i a caller ORs it in with
+ * tsdf_free_observe(seen, depth_out + i W H, ...): with margin == truncation and max_depth >= 2 far the new
+ * bits on state-0 voxels then number exactly gain[i].
+ * Required: dims each in 1 .. 2048, nx ny nz <= 2^28, the box inside the int16 block range; width / height in
+ * 1 .. the engine's max_width / max_height; V in 0 .. 4096 and V W H <= 2^26; far > 0, step > 0, margin >= 0,
+ * miss_depth 0 or in (0, far], all finite; mem_kind one of the two; e, cfg and state non-NULL, views and gain
+ * non-NULL when V > 0. Anything else is TSDF_ERR_INVALID_ARG with nothing written. V == 0 returns TSDF_OK.
+ * state, seen and depth_out are mem_kind memory alike; cfg, views and gain are host memory. With host arrays
+ * the call copies up and down; either way it has synchronised the engine stream once when it returns.
+ * Views are taken TSDF_VIEW_BATCH at a time, fewer while a batch's W H pixels exceed TSDF_VIEW_BATCH_PIXELS
+ * (at least one): the scratch holds 8 bytes per pixel of a batch, 72 bytes per view and, for host arrays,
+ * their staging. A cam_T_world that is no rotation (|n2 - 1| > 2^-10) goes without the brick cull and gives
+ * the same result. The call never touches the volume: the engine lends its stream and scratch (grown on
+ * demand, freed by tsdf_destroy), no status bits are set, pending pipelined frames stay pending, and a shard
+ * engine (shard_count > 1) serves as well as any other. */
+#define TSDF_VIEW_BATCH 64
+#define TSDF_VIEW_BATCH_PIXELS (1 << 22)
+typedef struct tsdf_view_config {
+  int32_t origin[3];   /* the box of `state` (and of `seen`), global voxels */
+  int32_t dims[3];     /* nx, ny, nz */
+  int32_t width, height;
+  tsdf_intrinsics K;   /* of every candidate view */
+  float far;           /* > 0 [m]: how deep a ray is marched */
+  float step;          /* > 0 [m]: sample spacing along the optical axis */
+  float margin;        /* >= 0 [m]: a voxel counts when range * (d - hz) >= margin; the engine's
+                          truncation gives tsdf_free_observe's own test */
+  float miss_depth;    /* depth of a ray that meets no surface: 0 (no return, nothing seen along it) or
+                          in (0, far] (the optimistic sensor: free out to there) */
+} tsdf_view_config;
+/* far 3, step = voxel_size, margin = truncation, miss_depth = far; origin, dims, width, height and K zero */
+void tsdf_view_config_default(const tsdf_engine* e, tsdf_view_config* cfg);
+int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* state,
+                   const uint32_t* seen /* may be NULL */, const tsdf_pose* views /* host, V cam_T_world */,
+                   int32_t V, int64_t* gain /* host, V */, float* depth_out /* V*H*W, may be NULL */,
+                   int mem_kind /* state, seen and depth_out alike */);
+
 int tsdf_get_stats(tsdf_engine* e, tsdf_stats* out, int clear_status);
 int tsdf_synchronize(tsdf_engine* e);
 /* mode TSDF_PROFILE_PHASES: HIP events between all four phases of an integrate call;
