@@ -15,6 +15,11 @@ constexpr int kFreeBrickX = 64, kFreeBrickY = 8, kFreeBrickZ = 8;
 // The radius of a brick's bounding sphere in voxels: half its diagonal, sqrt(31.5^2 + 3.5^2 + 3.5^2) = 31.89,
 // grown by one voxel and rounded up.
 constexpr float kFreeBrickRadius = 33.0f;
+// the launch grid of a workgroup per brick over a box (host side)
+inline dim3 free_brick_grid(int nx, int ny, int nz) {
+  return dim3((unsigned)((nx + kFreeBrickX - 1) / kFreeBrickX), (unsigned)((ny + kFreeBrickY - 1) / kFreeBrickY),
+              (unsigned)((nz + kFreeBrickZ - 1) / kFreeBrickZ));
+}
 // state bytes a lane of k_free_apply takes, 256 apart
 constexpr int kFreeApplyChunk = 16;
 

@@ -15,6 +15,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "disinfect_tsdf.h"
+#include "tsdf_box.h"
 #include "tsdf_internal.h"
 #include "tsdf_kernels.h"
 #include "tsdf_resolve.h"
@@ -72,8 +73,14 @@ inline int16_t h_f2s(float f) {
   if (f <= -32768.0f) return -32768;
   return (int16_t)f;
 }
-// sections of a staging buffer are 16-byte aligned
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+// tsdf_box.h stands alone: its constants are the public header's and the kernels'
+static_assert(kBoxMaxDim == TSDF_BOX_MAX_DIM && kBoxMaxVoxels == TSDF_BOX_MAX_VOXELS, "the public box limits");
+static_assert(kBoxBlockBits == kBlockLenBits, "box_in_block_range's block");
+// the limits as every box call's error text states them
+#define TSDF_STR_(x) #x
+#define TSDF_STR(x) TSDF_STR_(x)
+#define BOX_LIMITS_TEXT "dims 1.." TSDF_STR(TSDF_BOX_MAX_DIM) ", at most 2^28 voxels"
+static_assert(TSDF_BOX_MAX_VOXELS == (int64_t)1 << 28, "BOX_LIMITS_TEXT");
 
 template <typename T>
 hipError_t dmalloc(T** p, size_t count) {
@@ -118,6 +125,34 @@ template <typename... B>
 void release_all(B&... b) {
   (b.release(), ...);
 }
+
+// Host-or-device staging of a box call's arrays over its Sections (DESIGN.md "Box calls"). A device call hands
+// the kernels the caller's pointers; a host call stages each array in a section of the scratch buffer, uploads
+// inputs before and downloads outputs after. A null optional array takes no room and yields null either way.
+// The helpers enqueue only the copy they name, where they are called: the order of a call's copies, memsets
+// and launches, and its one synchronisation, stay the call's own.
+inline size_t staged(bool host, const void* p, size_t bytes) { return host && p ? bytes : 0; }
+struct Stage {
+  const Sections& L;
+  void* base;
+  bool host;
+  hipStream_t s;
+  // the device pointer of an output array (or of an input whose upload is not due yet)
+  template <typename T>
+  T* ptr(int h, T* p) const {
+    return !p ? nullptr : host ? L.at<T>(base, h) : p;
+  }
+  // the device pointer of an input array in *dev, its upload enqueued for a host call
+  template <typename T, typename U>
+  hipError_t in(int h, T* p, size_t bytes, U** dev) const {
+    *dev = ptr(h, p);
+    return host && p ? hipMemcpyAsync(L.at<void>(base, h), p, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  }
+  // the download of an output array from the pointer ptr / in gave, for a host call
+  hipError_t back(void* p, const void* dev, size_t bytes) const {
+    return host && p ? hipMemcpyAsync(p, dev, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+  }
+};
 
 // roctx ranges around the C-ABI calls (SURVEY.md 5 tracing): host-side enqueue intervals that
 // `rocprofv3 --marker-trace` lines up with the kernels they launch. Off unless TSDF_ROCTX=1.

@@ -163,11 +163,13 @@ int tsdf_surface_normals(tsdf_engine* e, const float* points, int64_t n, float s
   float* out = normals;
   const size_t bytes = (size_t)n * 12;
   if (mem_kind == TSDF_MEM_HOST) {
-    int rc = track_stage(e, 2 * up16(bytes));
+    Sections L;
+    const int h_p = L.add(bytes), h_out = L.add(bytes);
+    int rc = track_stage(e, L.total());
     if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(e->tk_stage, points, bytes, hipMemcpyHostToDevice, s));
-    p = reinterpret_cast<const float*>(e->tk_stage.p);
-    out = reinterpret_cast<float*>(e->tk_stage + up16(bytes));
+    HIP_OK(hipMemcpyAsync(L.at<float>(e->tk_stage.p, h_p), points, bytes, hipMemcpyHostToDevice, s));
+    p = L.at<float>(e->tk_stage.p, h_p);
+    out = L.at<float>(e->tk_stage.p, h_out);
   }
   hipLaunchKernelGGL(k_point_normals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, e->D, p, n,
                      e->cfg.voxel_size, sample_offset, out);
@@ -202,15 +204,16 @@ int tsdf_uv_dose(tsdf_engine* e, const float* points, const float* normals, int6
   if (n == 0 || m == 0) return TSDF_OK;
   if (mem_kind == TSDF_MEM_DEVICE) return dose_launch(e, points, normals, n, emitters, m, c, dose);
   hipStream_t s = e->stream;
-  const size_t b3 = up16((size_t)n * 12), b1 = up16((size_t)n * 4);
-  int rc = track_stage(e, 2 * b3 + b1);
+  Sections L;
+  const int h_p = L.add((size_t)n * 12), h_nr = L.add((size_t)n * 12), h_d = L.add((size_t)n * 4);
+  int rc = track_stage(e, L.total());
   if (rc) return rc;
   uint8_t* b = e->tk_stage;
-  float* d = reinterpret_cast<float*>(b + 2 * b3);
-  HIP_OK(hipMemcpyAsync(b, points, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(b + b3, normals, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  float *p = L.at<float>(b, h_p), *nr = L.at<float>(b, h_nr), *d = L.at<float>(b, h_d);
+  HIP_OK(hipMemcpyAsync(p, points, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(nr, normals, (size_t)n * 12, hipMemcpyHostToDevice, s));
   HIP_OK(hipMemcpyAsync(d, dose, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  rc = dose_launch(e, reinterpret_cast<const float*>(b), reinterpret_cast<const float*>(b + b3), n, emitters, m, c, d);
+  rc = dose_launch(e, p, nr, n, emitters, m, c, d);
   if (rc) return rc;
   HIP_OK(hipMemcpyAsync(dose, d, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));

@@ -12,21 +12,10 @@ void tsdf_edt_config_default(tsdf_edt_config* c) {
 
 namespace {
 
-constexpr int kEdtMaxDim = 2048;
-constexpr int64_t kEdtMaxVoxels = (int64_t)1 << 28;
-
 bool edt_args_ok(const tsdf_edt_config& c) {
-  int64_t n = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (c.dims[a] < 1 || c.dims[a] > kEdtMaxDim) return false;
-    n *= c.dims[a];
-    // the box grown by one voxel, in blocks
-    const int64_t lo = ((int64_t)c.origin[a] - 1) >> kBlockLenBits;
-    const int64_t hi = ((int64_t)c.origin[a] + c.dims[a]) >> kBlockLenBits;
-    if (lo < -32768 || hi > 32767) return false;
-  }
-  return n <= kEdtMaxVoxels && c.max_dist >= 1 && c.max_dist <= 255 && c.min_weight >= 0 &&
-         (c.sites == TSDF_EDT_SURFACE || c.sites == (TSDF_EDT_SURFACE | TSDF_EDT_UNKNOWN));
+  // (the box grown by one voxel: a surface voxel's face neighbours are read)
+  return box_dims_ok(c.dims) && box_in_block_range(c.origin, c.dims, 1) && c.max_dist >= 1 && c.max_dist <= 255 &&
+         c.min_weight >= 0 && (c.sites == TSDF_EDT_SURFACE || c.sites == (TSDF_EDT_SURFACE | TSDF_EDT_UNKNOWN));
 }
 
 // one y or z pass: lines of L elements `stride` apart, ncol side by side in each of `slabs` slabs
@@ -57,7 +46,7 @@ int line_pass(hipStream_t s, int64_t ncol, int64_t stride, int64_t slab, int sla
 int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_edt_out* out) {
   TraceRange trace_("tsdf_distance_field");
   if (!e || !cfg || !out || !out->d2 || !mem_kind_ok(out->mem_kind) || !edt_args_ok(*cfg)) {
-    set_error("tsdf_distance_field: invalid argument (dims 1..2048, at most 2^28 voxels, the box inside the block "
+    set_error("tsdf_distance_field: invalid argument (" BOX_LIMITS_TEXT ", the box inside the block "
               "range, max_dist 1..255, min_weight >= 0, sites SURFACE or SURFACE | UNKNOWN, d2 non-NULL)");
     return TSDF_ERR_INVALID_ARG;
   }
@@ -77,19 +66,21 @@ int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_e
   B.R = c.max_dist;
   B.min_weight = c.min_weight;
   B.unknown = (c.sites & TSDF_EDT_UNKNOWN) ? 1 : 0;
-  const size_t n = (size_t)B.nx * B.ny * B.nz;
+  const size_t n = box_voxels(c.dims), b_bits = (size_t)B.ny * B.nz * B.rowbytes;
   const bool host = out->mem_kind == TSDF_MEM_HOST;
   // sections: bitmap | x pass (u8) | y pass (u16) | host outputs' staging: d2, state
-  const size_t b_bits = up16((size_t)B.ny * B.nz * B.rowbytes), b_g = up16(n), b_t = up16(2 * n);
-  const size_t b_stage = host ? up16(2 * n) + (out->state ? up16(n) : 0) : 0;
-  int rc = e->edt_buf.ensure(b_bits + b_g + b_t + b_stage, "tsdf_distance_field: hipMalloc edt_buf");
+  Sections L;
+  const int h_bits = L.add(b_bits), h_g = L.add(n), h_t = L.add(2 * n);
+  const int h_d2 = L.add(staged(host, out->d2, 2 * n)), h_state = L.add(staged(host, out->state, n));
+  int rc = e->edt_buf.ensure(L.total(), "tsdf_distance_field: hipMalloc edt_buf");
   if (rc) return rc;
-  uint8_t* bits = e->edt_buf;
-  uint8_t* g = bits + b_bits;
-  uint16_t* t = reinterpret_cast<uint16_t*>(g + b_g);
-  uint16_t* d2 = host ? reinterpret_cast<uint16_t*>(g + b_g + b_t) : out->d2;
-  uint8_t* state = !out->state ? nullptr : (host ? g + b_g + b_t + up16(2 * n) : out->state);
-  HIP_OK(hipMemsetAsync(bits, 0, b_bits, s));
+  const Stage St{L, e->edt_buf.p, host, s};
+  uint8_t* bits = L.at<uint8_t>(St.base, h_bits);
+  uint8_t* g = L.at<uint8_t>(St.base, h_g);
+  uint16_t* t = L.at<uint16_t>(St.base, h_t);
+  uint16_t* d2 = St.ptr(h_d2, out->d2);
+  uint8_t* state = St.ptr(h_state, out->state);
+  HIP_OK(hipMemsetAsync(bits, 0, L.size(h_bits), s));
   if (state) HIP_OK(hipMemsetAsync(state, 0, n, s));
   hipLaunchKernelGGL(k_edt_classify, dim3((unsigned)(B.cbx * B.cby * B.cbz)), dim3(256), 0, s, e->D, B, bits, state);
   LAUNCH_OK("k_edt_classify");
@@ -101,10 +92,8 @@ int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_e
   if (rc) return rc;
   rc = line_pass<uint16_t>(s, nxy, nxy, 0, 1, B.nz, B.R, t, d2);   // along z: every (y, x) a line
   if (rc) return rc;
-  if (host) {
-    HIP_OK(hipMemcpyAsync(out->d2, d2, 2 * n, hipMemcpyDeviceToHost, s));
-    if (state) HIP_OK(hipMemcpyAsync(out->state, state, n, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-  }
+  HIP_OK(St.back(out->d2, d2, 2 * n));
+  HIP_OK(St.back(out->state, state, n));
+  if (host) HIP_OK(hipStreamSynchronize(s));
   return TSDF_OK;
 }

@@ -169,16 +169,16 @@ int tsdf_extract_mesh_indexed(tsdf_engine* e, const float* bounds, float missing
   }
   if (dev_out) return TSDF_OK;
   // host output: the passes write a staging buffer (sections 16-byte aligned), copied out per array
-  const size_t o_pos = 0, o_idx = o_pos + up16((size_t)nv * 12), o_rgba = o_idx + up16((size_t)nt * 12),
-               o_prob = o_rgba + up16((size_t)nv * 4), o_keys = o_prob + up16((size_t)nv * 4),
-               bytes = o_keys + up16((size_t)nv * 16);
-  if (int rc = e->mi_out.ensure(bytes, "tsdf_extract_mesh_indexed: hipMalloc mi_out")) return rc;
+  Sections L;  // (every array has its section, asked for or not)
+  const int h_pos = L.add((size_t)nv * 12), h_idx = L.add((size_t)nt * 12), h_rgba = L.add((size_t)nv * 4),
+            h_prob = L.add((size_t)nv * 4), h_keys = L.add((size_t)nv * 16);
+  if (int rc = e->mi_out.ensure(L.total(), "tsdf_extract_mesh_indexed: hipMalloc mi_out")) return rc;
   uint8_t* b = e->mi_out;
-  const MeshIndexedOut S{reinterpret_cast<float*>(b + o_pos),
-                         out->rgba ? b + o_rgba : nullptr,
-                         out->prob ? reinterpret_cast<float*>(b + o_prob) : nullptr,
-                         out->keys ? reinterpret_cast<int32_t*>(b + o_keys) : nullptr,
-                         reinterpret_cast<int32_t*>(b + o_idx),
+  const MeshIndexedOut S{L.at<float>(b, h_pos),
+                         out->rgba ? L.at<uint8_t>(b, h_rgba) : nullptr,
+                         out->prob ? L.at<float>(b, h_prob) : nullptr,
+                         out->keys ? L.at<int32_t>(b, h_keys) : nullptr,
+                         L.at<int32_t>(b, h_idx),
                          nv,
                          nt};
   emit(S);

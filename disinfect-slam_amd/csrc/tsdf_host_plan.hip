@@ -110,15 +110,16 @@ int tsdf_uv_irradiance(tsdf_engine* e, const float* points, const float* normals
   if (n == 0 || C == 0) return TSDF_OK;
   if (mem_kind == TSDF_MEM_DEVICE) return irradiance_launch(e, points, normals, n, emitters, first, C, c, out);
   hipStream_t s = e->stream;
-  const size_t b3 = up16((size_t)n * 12), bo = (size_t)C * (size_t)n * 4;
-  int rc = track_stage(e, 2 * b3 + bo);
+  const size_t bo = (size_t)C * (size_t)n * 4;
+  Sections L;
+  const int h_p = L.add((size_t)n * 12), h_nr = L.add((size_t)n * 12), h_d = L.add(bo);
+  int rc = track_stage(e, L.total());
   if (rc) return rc;
   uint8_t* b = e->tk_stage;
-  float* d = reinterpret_cast<float*>(b + 2 * b3);
-  HIP_OK(hipMemcpyAsync(b, points, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(b + b3, normals, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  rc = irradiance_launch(e, reinterpret_cast<const float*>(b), reinterpret_cast<const float*>(b + b3), n, emitters,
-                         first, C, c, d);
+  float *p = L.at<float>(b, h_p), *nr = L.at<float>(b, h_nr), *d = L.at<float>(b, h_d);
+  HIP_OK(hipMemcpyAsync(p, points, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(nr, normals, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  rc = irradiance_launch(e, p, nr, n, emitters, first, C, c, d);
   if (rc) return rc;
   HIP_OK(hipMemcpyAsync(out, d, bo, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
@@ -161,17 +162,19 @@ int tsdf_uv_plan(tsdf_engine* e, const float* irradiance, int32_t C, int64_t n, 
   P.E = irradiance;
   P.need = need;
   P.weight = weight;
-  const size_t bE = up16((size_t)C * (size_t)n * 4), b1 = up16((size_t)n * 4);
   if (mem_kind == TSDF_MEM_HOST) {
-    rc = e->pl_stage.ensure(bE + 2 * b1, "tsdf_uv_plan: hipMalloc pl_stage");
+    Sections L;  // (the weights have their section, given or not)
+    const int h_E = L.add((size_t)C * (size_t)n * 4), h_need = L.add((size_t)n * 4), h_w = L.add((size_t)n * 4);
+    rc = e->pl_stage.ensure(L.total(), "tsdf_uv_plan: hipMalloc pl_stage");
     if (rc) return rc;
     uint8_t* b = e->pl_stage;
-    HIP_OK(hipMemcpyAsync(b, irradiance, (size_t)C * (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(b + bE, need, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (weight) HIP_OK(hipMemcpyAsync(b + bE + b1, weight, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    P.E = reinterpret_cast<const float*>(b);
-    P.need = reinterpret_cast<float*>(b + bE);
-    P.weight = weight ? reinterpret_cast<const float*>(b + bE + b1) : nullptr;
+    float *dE = L.at<float>(b, h_E), *dneed = L.at<float>(b, h_need), *dw = L.at<float>(b, h_w);
+    HIP_OK(hipMemcpyAsync(dE, irradiance, (size_t)C * (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(dneed, need, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (weight) HIP_OK(hipMemcpyAsync(dw, weight, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    P.E = dE;
+    P.need = dneed;
+    P.weight = weight ? dw : nullptr;
   }
   P.n = n;
   P.C = C;

@@ -87,15 +87,13 @@ int tsdf_raycast_surface(tsdf_engine* e, const tsdf_intrinsics* K, int W, int H,
                           SurfaceOut{out->point, out->normal, out->depth, out->prob, reinterpret_cast<uint32_t*>(out->rgbw)});
   // host maps: a staging buffer (sections 16-byte aligned), copied out per map
   const size_t n = (size_t)W * H;
-  const size_t o_nrm = up16(n * 12), o_dep = o_nrm + up16(n * 12), o_prob = o_dep + up16(n * 4),
-               o_rgbw = o_prob + up16(n * 4);
-  int rc = track_stage(e, o_rgbw + up16(n * 4));
+  Sections L;  // (every map has its section, asked for or not)
+  const int h_pt = L.add(n * 12), h_nrm = L.add(n * 12), h_dep = L.add(n * 4), h_prob = L.add(n * 4), h_rgbw = L.add(n * 4);
+  int rc = track_stage(e, L.total());
   if (rc) return rc;
   uint8_t* b = e->tk_stage;
-  const SurfaceOut S{reinterpret_cast<float*>(b), reinterpret_cast<float*>(b + o_nrm),
-                     out->depth ? reinterpret_cast<float*>(b + o_dep) : nullptr,
-                     out->prob ? reinterpret_cast<float*>(b + o_prob) : nullptr,
-                     out->rgbw ? reinterpret_cast<uint32_t*>(b + o_rgbw) : nullptr};
+  const SurfaceOut S{L.at<float>(b, h_pt), L.at<float>(b, h_nrm), out->depth ? L.at<float>(b, h_dep) : nullptr,
+                     out->prob ? L.at<float>(b, h_prob) : nullptr, out->rgbw ? L.at<uint32_t>(b, h_rgbw) : nullptr};
   rc = surface_launch(e, K, W, H, pose, max_depth, S);
   if (rc) return rc;
   hipStream_t s = e->stream;
@@ -124,16 +122,16 @@ int tsdf_icp_linearize(tsdf_engine* e, const float* depth, int W, int H, const t
   const float *d = depth, *pt = model->point, *nr = model->normal;
   if (mem_kind == TSDF_MEM_HOST) {
     const size_t n = (size_t)W * H, nm = (size_t)model->width * model->height;
-    const size_t o_pt = up16(n * 4), o_nr = o_pt + up16(nm * 12);
-    int rc = track_stage(e, o_nr + up16(nm * 12));
+    Sections L;
+    const int h_d = L.add(n * 4), h_pt = L.add(nm * 12), h_nr = L.add(nm * 12);
+    int rc = track_stage(e, L.total());
     if (rc) return rc;
     uint8_t* b = e->tk_stage;
-    HIP_OK(hipMemcpyAsync(b, depth, n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_OK(hipMemcpyAsync(b + o_pt, model->point, nm * 12, hipMemcpyHostToDevice, e->stream));
-    HIP_OK(hipMemcpyAsync(b + o_nr, model->normal, nm * 12, hipMemcpyHostToDevice, e->stream));
-    d = reinterpret_cast<const float*>(b);
-    pt = reinterpret_cast<const float*>(b + o_pt);
-    nr = reinterpret_cast<const float*>(b + o_nr);
+    float *sd = L.at<float>(b, h_d), *spt = L.at<float>(b, h_pt), *snr = L.at<float>(b, h_nr);
+    HIP_OK(hipMemcpyAsync(sd, depth, n * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync(spt, model->point, nm * 12, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync(snr, model->normal, nm * 12, hipMemcpyHostToDevice, e->stream));
+    d = sd, pt = spt, nr = snr;
   }
   return icp_launch(e, d, W, H, K, pose, pt, nr, model->width, model->height, &model->K, &model->cam_T_world, stride,
                     max_dist, max_depth, out29);
@@ -152,16 +150,17 @@ int tsdf_point_map_normals(tsdf_engine* e, const tsdf_intrinsics* K, int W, int 
   const float max_depth = 1.0f;  // not read by the kernel
   if (mem_kind == TSDF_MEM_DEVICE) return normals_launch(e, K, W, H, pose, max_depth, point, normal, out);
   // host maps: staged (sections 16-byte aligned), the result copied out
-  const size_t n = (size_t)W * H, o_nr = up16(n * 12), o_out = o_nr + up16(n * 12);
-  int rc = track_stage(e, o_out + up16(n * 12));
+  const size_t n = (size_t)W * H;
+  Sections L;
+  const int h_pt = L.add(n * 12), h_nr = L.add(n * 12), h_out = L.add(n * 12);
+  int rc = track_stage(e, L.total());
   if (rc) return rc;
   uint8_t* b = e->tk_stage;
-  HIP_OK(hipMemcpyAsync(b, point, n * 12, hipMemcpyHostToDevice, e->stream));
-  HIP_OK(hipMemcpyAsync(b + o_nr, normal, n * 12, hipMemcpyHostToDevice, e->stream));
-  rc = normals_launch(e, K, W, H, pose, max_depth, reinterpret_cast<const float*>(b),
-                      reinterpret_cast<const float*>(b + o_nr), reinterpret_cast<float*>(b + o_out));
+  HIP_OK(hipMemcpyAsync(L.at<float>(b, h_pt), point, n * 12, hipMemcpyHostToDevice, e->stream));
+  HIP_OK(hipMemcpyAsync(L.at<float>(b, h_nr), normal, n * 12, hipMemcpyHostToDevice, e->stream));
+  rc = normals_launch(e, K, W, H, pose, max_depth, L.at<float>(b, h_pt), L.at<float>(b, h_nr), L.at<float>(b, h_out));
   if (rc) return rc;
-  HIP_OK(hipMemcpyAsync(out, b + o_out, n * 12, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(out, L.at<float>(b, h_out), n * 12, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   return TSDF_OK;
 }

@@ -13,8 +13,6 @@ void tsdf_travel_config_default(tsdf_travel_config* c) {
 
 namespace {
 
-constexpr int kTravelMaxDim = 2048;
-constexpr int64_t kTravelMaxVoxels = (int64_t)1 << 28;
 // rounds enqueued between two reads of the control words
 constexpr int kTravelBatch = 32;
 
@@ -28,25 +26,16 @@ bool travel_log() {
   return on;
 }
 
-bool travel_dims_ok(const int32_t* dims) {
-  int64_t n = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > kTravelMaxDim) return false;
-    n *= dims[a];
-  }
-  return n <= kTravelMaxVoxels;
-}
-
 }  // namespace
 
 int tsdf_travel_field(tsdf_engine* e, const tsdf_travel_config* cfg, const uint16_t* d2, const uint8_t* state,
                       const int32_t* seeds, int32_t S, uint32_t* cost, int mem_kind, int32_t* seeded,
                       int32_t* rounds) {
   TraceRange trace_("tsdf_travel_field");
-  if (!e || !cfg || !d2 || !state || !cost || !mem_kind_ok(mem_kind) || !travel_dims_ok(cfg->dims) ||
+  if (!e || !cfg || !d2 || !state || !cost || !mem_kind_ok(mem_kind) || !box_dims_ok(cfg->dims) ||
       cfg->clearance2 < 0 || cfg->clearance2 > 255 * 255 || (cfg->unknown_free != 0 && cfg->unknown_free != 1) ||
       S < 0 || (S > 0 && !seeds)) {
-    set_error("tsdf_travel_field: invalid argument (dims 1..2048, at most 2^28 voxels, clearance2 0..65025, "
+    set_error("tsdf_travel_field: invalid argument (" BOX_LIMITS_TEXT ", clearance2 0..65025, "
               "unknown_free 0 or 1, d2, state and cost non-NULL, S >= 0 with seeds)");
     return TSDF_ERR_INVALID_ARG;
   }
@@ -54,34 +43,30 @@ int tsdf_travel_field(tsdf_engine* e, const tsdf_travel_config* cfg, const uint1
   hipStream_t s = e->stream;
   TravelArgs A{};
   A.nx = cfg->dims[0], A.ny = cfg->dims[1], A.nz = cfg->dims[2];
-  A.tx = (A.nx + kTravelTile - 1) >> kTravelTileBits;
-  A.ty = (A.ny + kTravelTile - 1) >> kTravelTileBits;
-  A.tz = (A.nz + kTravelTile - 1) >> kTravelTileBits;
+  A.tx = box_tiles(A.nx, kTravelTileBits), A.ty = box_tiles(A.ny, kTravelTileBits), A.tz = box_tiles(A.nz, kTravelTileBits);
   A.clearance2 = cfg->clearance2;
   A.unknown_free = cfg->unknown_free;
-  const size_t n = (size_t)A.nx * A.ny * A.nz, tiles = (size_t)A.tx * A.ty * A.tz;
+  const size_t n = box_voxels(cfg->dims), tiles = (size_t)A.tx * A.ty * A.tz;
   const bool host = mem_kind == TSDF_MEM_HOST;
   // sections: control words | stamps | two lists | seeds | host arrays' staging: cost, d2, state
-  const size_t b_ctl = up16(sizeof(TravelCtl)), b_tiles = up16(4 * tiles), b_seeds = up16((size_t)S * 12);
-  const size_t b_stage = host ? up16(4 * n) + up16(2 * n) + up16(n) : 0;
-  int rc = e->tv_buf.ensure(b_ctl + 3 * b_tiles + b_seeds + b_stage, "tsdf_travel_field: hipMalloc tv_buf");
+  Sections L;
+  const int h_ctl = L.add(sizeof(TravelCtl)), h_stamp = L.add(4 * tiles), h_list0 = L.add(4 * tiles),
+            h_list1 = L.add(4 * tiles), h_seeds = L.add((size_t)S * 12);
+  const int h_cost = L.add(staged(host, cost, 4 * n)), h_d2 = L.add(staged(host, d2, 2 * n)),
+            h_state = L.add(staged(host, state, n));
+  int rc = e->tv_buf.ensure(L.total(), "tsdf_travel_field: hipMalloc tv_buf");
   if (rc) return rc;
-  uint8_t* b = e->tv_buf;
-  A.ctl = reinterpret_cast<TravelCtl*>(b);
-  A.stamp = reinterpret_cast<uint32_t*>(b + b_ctl);
-  A.list[0] = reinterpret_cast<uint32_t*>(b + b_ctl + b_tiles);
-  A.list[1] = reinterpret_cast<uint32_t*>(b + b_ctl + 2 * b_tiles);
-  int32_t* dseeds = reinterpret_cast<int32_t*>(b + b_ctl + 3 * b_tiles);
-  uint8_t* stage = b + b_ctl + 3 * b_tiles + b_seeds;
-  A.cost = host ? reinterpret_cast<uint32_t*>(stage) : cost;
-  A.d2 = host ? reinterpret_cast<const uint16_t*>(stage + up16(4 * n)) : d2;
-  A.state = host ? stage + up16(4 * n) + up16(2 * n) : state;
-  if (host) {
-    HIP_OK(hipMemcpyAsync(stage + up16(4 * n), d2, 2 * n, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(stage + up16(4 * n) + up16(2 * n), state, n, hipMemcpyHostToDevice, s));
-  }
-  // (the control words and the stamps are one range)
-  HIP_OK(hipMemsetAsync(b, 0, b_ctl + b_tiles, s));
+  const Stage St{L, e->tv_buf.p, host, s};
+  A.ctl = L.at<TravelCtl>(St.base, h_ctl);
+  A.stamp = L.at<uint32_t>(St.base, h_stamp);
+  A.list[0] = L.at<uint32_t>(St.base, h_list0);
+  A.list[1] = L.at<uint32_t>(St.base, h_list1);
+  int32_t* dseeds = L.at<int32_t>(St.base, h_seeds);
+  A.cost = St.ptr(h_cost, cost);
+  HIP_OK(St.in(h_d2, d2, 2 * n, &A.d2));
+  HIP_OK(St.in(h_state, state, n, &A.state));
+  // (the control words and the stamps are one range: sections are contiguous)
+  HIP_OK(hipMemsetAsync(A.ctl, 0, L.size(h_ctl) + L.size(h_stamp), s));
   HIP_OK(hipMemsetAsync(A.cost, 0xFF, 4 * n, s));
   if (S > 0) {
     HIP_OK(hipMemcpyAsync(dseeds, seeds, (size_t)S * 12, hipMemcpyHostToDevice, s));
@@ -111,10 +96,8 @@ int tsdf_travel_field(tsdf_engine* e, const tsdf_travel_config* cfg, const uint1
       return TSDF_ERR_HIP;
     }
   }
-  if (host) {
-    HIP_OK(hipMemcpyAsync(cost, A.cost, 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-  }
+  HIP_OK(St.back(cost, A.cost, 4 * n));
+  if (host) HIP_OK(hipStreamSynchronize(s));
   if (seeded) *seeded = (int32_t)ctl.seeded;
   if (rounds) *rounds = (int32_t)ctl.rounds;
   return TSDF_OK;
@@ -123,9 +106,10 @@ int tsdf_travel_field(tsdf_engine* e, const tsdf_travel_config* cfg, const uint1
 int tsdf_travel_paths(tsdf_engine* e, const int32_t dims[3], const uint32_t* cost, int mem_kind,
                       const int32_t* targets, int32_t T, int32_t max_len, int32_t* path, int32_t* len) {
   TraceRange trace_("tsdf_travel_paths");
-  if (!e || !dims || !cost || !mem_kind_ok(mem_kind) || !travel_dims_ok(dims) || T < 0 || max_len < 0 ||
-      (int64_t)T * max_len > ((int64_t)1 << 28) || (T > 0 && (!targets || !len || (max_len > 0 && !path)))) {
-    set_error("tsdf_travel_paths: invalid argument (dims 1..2048, at most 2^28 voxels, T >= 0, max_len >= 0, "
+  // (a walk visits a voxel once, so a box's voxels bound one target's path: the cap on T * max_len)
+  if (!e || !dims || !cost || !mem_kind_ok(mem_kind) || !box_dims_ok(dims) || T < 0 || max_len < 0 ||
+      (int64_t)T * max_len > kBoxMaxVoxels || (T > 0 && (!targets || !len || (max_len > 0 && !path)))) {
+    set_error("tsdf_travel_paths: invalid argument (" BOX_LIMITS_TEXT ", T >= 0, max_len >= 0, "
               "T * max_len <= 2^28, cost, targets, path and len non-NULL)");
     return TSDF_ERR_INVALID_ARG;
   }
@@ -139,13 +123,15 @@ int tsdf_travel_paths(tsdf_engine* e, const int32_t dims[3], const uint32_t* cos
   HIP_OK(hipSetDevice(e->device));
   hipStream_t s = e->stream;
   // sections: targets | lengths | paths
-  const size_t b_t = up16((size_t)T * 12), b_l = up16((size_t)T * 4), b_p = (size_t)T * (size_t)max_len * 4;
-  int rc = e->tv_buf.ensure(b_t + b_l + b_p, "tsdf_travel_paths: hipMalloc tv_buf");
+  const size_t b_p = (size_t)T * (size_t)max_len * 4;
+  Sections L;
+  const int h_t = L.add((size_t)T * 12), h_l = L.add((size_t)T * 4), h_p = L.add(b_p);
+  int rc = e->tv_buf.ensure(L.total(), "tsdf_travel_paths: hipMalloc tv_buf");
   if (rc) return rc;
   uint8_t* b = e->tv_buf;
-  int32_t* dt = reinterpret_cast<int32_t*>(b);
-  int32_t* dl = reinterpret_cast<int32_t*>(b + b_t);
-  int32_t* dp = reinterpret_cast<int32_t*>(b + b_t + b_l);
+  int32_t* dt = L.at<int32_t>(b, h_t);
+  int32_t* dl = L.at<int32_t>(b, h_l);
+  int32_t* dp = L.at<int32_t>(b, h_p);
   HIP_OK(hipMemcpyAsync(dt, targets, (size_t)T * 12, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_travel_paths, dim3((unsigned)((T + 63) / 64)), dim3(64), 0, s, cost, dims[0], dims[1], dims[2],
                      dt, (int)T, max_len, dp, dl);

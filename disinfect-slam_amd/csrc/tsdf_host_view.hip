@@ -22,23 +22,8 @@ void tsdf_view_config_default(const tsdf_engine* e, tsdf_view_config* c) {
 
 namespace {
 
-constexpr int kViewMaxDim = 2048;
-constexpr int64_t kViewMaxVoxels = (int64_t)1 << 28;
 constexpr int kViewMaxViews = 4096, kViewMaxSamples = 65536;
 constexpr int64_t kViewMaxPixels = (int64_t)1 << 26;  // V * W * H
-
-// dims 1..2048, at most 2^28 voxels, every voxel of the box in a block of the int16 block range
-bool view_box_ok(const int32_t* origin, const int32_t* dims) {
-  int64_t n = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > kViewMaxDim) return false;
-    n *= dims[a];
-    const int64_t lo = (int64_t)origin[a] >> kBlockLenBits;
-    const int64_t hi = ((int64_t)origin[a] + dims[a] - 1) >> kBlockLenBits;
-    if (lo < -32768 || hi > 32767) return false;
-  }
-  return n <= kViewMaxVoxels;
-}
 
 }  // namespace
 
@@ -48,7 +33,7 @@ int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* s
   bool ok = e && cfg && state && mem_kind_ok(mem_kind) && V >= 0 && V <= kViewMaxViews && (V == 0 || (views && gain));
   int J = 0;
   if (ok) {
-    ok = view_box_ok(cfg->origin, cfg->dims) && cfg->width >= 1 && cfg->width <= e->cfg.max_width && cfg->height >= 1 &&
+    ok = box_dims_ok(cfg->dims) && box_in_block_range(cfg->origin, cfg->dims, 0) && cfg->width >= 1 && cfg->width <= e->cfg.max_width && cfg->height >= 1 &&
          cfg->height <= e->cfg.max_height && (int64_t)V * cfg->width * cfg->height <= kViewMaxPixels &&
          std::isfinite(cfg->far) && cfg->far > 0.0f && std::isfinite(cfg->step) && cfg->step > 0.0f &&
          std::isfinite(cfg->margin) && cfg->margin >= 0.0f && std::isfinite(cfg->miss_depth) &&
@@ -61,7 +46,7 @@ int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* s
     }
   }
   if (!ok) {
-    set_error("tsdf_view_gain: invalid argument (dims 1..2048, at most 2^28 voxels, the box inside the block range, "
+    set_error("tsdf_view_gain: invalid argument (" BOX_LIMITS_TEXT ", the box inside the block range, "
               "width and height 1..the engine's, V 0..4096, V * width * height <= 2^26, far and step > 0 with "
               "1 <= far / step <= 65536, margin >= 0, miss_depth 0..far, all finite, cfg and state non-NULL, views "
               "and gain with V > 0)");
@@ -72,13 +57,10 @@ int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* s
   hipStream_t s = e->stream;
   const int W = cfg->width, H = cfg->height;
   const size_t npix = (size_t)W * H;
-  const size_t n = (size_t)cfg->dims[0] * cfg->dims[1] * cfg->dims[2];
-  const int wx = (cfg->dims[0] + 31) >> 5;
-  const size_t words = (size_t)cfg->dims[2] * cfg->dims[1] * wx;
+  const size_t n = box_voxels(cfg->dims), words = (size_t)box_words(cfg->dims);
   const int batch = (int)std::min<int64_t>(kViewBatch, std::max<int64_t>(1, kViewBatchPixels / (int64_t)npix));
   const bool host = mem_kind == TSDF_MEM_HOST;
-  // the views as the kernels take them: make_params' world_T_cam, and the free layer's rule for a rigid motion
-  // (tsdf_host_free.hip: |n^2 - 1| <= 2^-10 stretches no length by more than 1 + 2^-9)
+  // the views as the kernels take them: make_params' world_T_cam, and the brick culls' rule for a rigid motion
   std::vector<ViewCam> cams((size_t)V);
   FrameParams P0{};
   for (int i = 0; i < V; ++i) {
@@ -87,28 +69,23 @@ int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* s
     ViewCam& c = cams[(size_t)i];
     c.cq = P.cq, c.ct = P.ct, c.wq = P.wq, c.wt = P.wt;
     c.dmax_bits = 0;
-    const double n2 = (double)P.cq.x * P.cq.x + (double)P.cq.y * P.cq.y + (double)P.cq.z * P.cq.z + (double)P.cq.w * P.cq.w;
-    c.rigid = std::fabs(n2 - 1.0) <= 0x1p-10 ? 1 : 0;
+    const float q[4] = {P.cq.x, P.cq.y, P.cq.z, P.cq.w};
+    c.rigid = pose_is_rigid(q) ? 1 : 0;
   }
   // sections: views | gains | a batch's pixel records | host arrays' staging: state, seen, a batch's depth
-  const size_t b_cam = up16((size_t)V * sizeof(ViewCam)), b_gain = up16((size_t)V * 8),
-               b_pix = up16((size_t)batch * npix * sizeof(FreePix)), b_state = host ? up16(n) : 0,
-               b_seen = host && seen ? up16(4 * words) : 0, b_depth = host && depth_out ? up16((size_t)batch * npix * 4) : 0;
-  int rc = e->vw_buf.ensure(b_cam + b_gain + b_pix + b_state + b_seen + b_depth, "tsdf_view_gain: hipMalloc vw_buf");
+  Sections L;
+  const int h_cam = L.add((size_t)V * sizeof(ViewCam)), h_gain = L.add((size_t)V * 8),
+            h_pix = L.add((size_t)batch * npix * sizeof(FreePix)), h_state = L.add(staged(host, state, n)),
+            h_seen = L.add(staged(host, seen, 4 * words)), h_depth = L.add(staged(host, depth_out, (size_t)batch * npix * 4));
+  int rc = e->vw_buf.ensure(L.total(), "tsdf_view_gain: hipMalloc vw_buf");
   if (rc) return rc;
-  uint8_t* b = e->vw_buf;
-  ViewCam* dcam = reinterpret_cast<ViewCam*>(b);
-  unsigned long long* dgain = reinterpret_cast<unsigned long long*>(b + b_cam);
-  FreePix* dpix = reinterpret_cast<FreePix*>(b + b_cam + b_gain);
-  uint8_t* dstate = b + b_cam + b_gain + b_pix;
-  uint32_t* dseen = reinterpret_cast<uint32_t*>(b + b_cam + b_gain + b_pix + b_state);
-  float* ddepth = reinterpret_cast<float*>(b + b_cam + b_gain + b_pix + b_state + b_seen);
+  const Stage St{L, e->vw_buf.p, host, s};
+  ViewCam* dcam = L.at<ViewCam>(St.base, h_cam);
+  unsigned long long* dgain = L.at<unsigned long long>(St.base, h_gain);
+  FreePix* dpix = L.at<FreePix>(St.base, h_pix);
+  float* ddepth = St.ptr(h_depth, depth_out);  // (a host call's: a batch's staging)
   HIP_OK(hipMemcpyAsync(dcam, cams.data(), (size_t)V * sizeof(ViewCam), hipMemcpyHostToDevice, s));
   HIP_OK(hipMemsetAsync(dgain, 0, (size_t)V * 8, s));
-  if (host) {
-    HIP_OK(hipMemcpyAsync(dstate, state, n, hipMemcpyHostToDevice, s));
-    if (seen) HIP_OK(hipMemcpyAsync(dseen, seen, 4 * words, hipMemcpyHostToDevice, s));
-  }
   ViewDepthArgs D{};
   D.ox = cfg->origin[0], D.oy = cfg->origin[1], D.oz = cfg->origin[2];
   D.nx = cfg->dims[0], D.ny = cfg->dims[1], D.nz = cfg->dims[2];
@@ -118,21 +95,20 @@ int tsdf_view_gain(tsdf_engine* e, const tsdf_view_config* cfg, const uint8_t* s
   D.step = cfg->step, D.miss = cfg->miss_depth;
   D.J = J;
   D.skip = e->env.view_skip ? 1 : 0;
-  D.state = host ? dstate : state;
+  HIP_OK(St.in(h_state, state, n, &D.state));
   D.pix = dpix;
   ViewGainArgs G{};
   G.ox = D.ox, G.oy = D.oy, G.oz = D.oz;
   G.nx = D.nx, G.ny = D.ny, G.nz = D.nz;
-  G.wx = wx;
+  G.wx = (G.nx + 31) >> 5;
   G.W = W, G.H = H;
   G.fx = P0.fx, G.fy = P0.fy, G.cx = P0.cx, G.cy = P0.cy;
   G.voxel = P0.voxel, G.margin = cfg->margin;
   G.cull = e->env.view_skip ? 1 : 0;
   G.state = D.state;
-  G.seen = seen ? (host ? dseen : seen) : nullptr;
+  HIP_OK(St.in(h_seen, seen, 4 * words, &G.seen));
   G.pix = dpix;
-  const dim3 bricks((unsigned)((G.nx + kFreeBrickX - 1) / kFreeBrickX), (unsigned)((G.ny + kFreeBrickY - 1) / kFreeBrickY),
-                    (unsigned)((G.nz + kFreeBrickZ - 1) / kFreeBrickZ));
+  const dim3 bricks = free_brick_grid(G.nx, G.ny, G.nz);
   for (int v0 = 0; v0 < V; v0 += batch) {
     const int nv = std::min(batch, V - v0);
     D.cam = dcam + v0;

@@ -218,23 +218,39 @@ std::vector<int32_t> TSDFGrid::PlanStops(const std::vector<float>& irradiance, i
   return stops;
 }
 
+namespace {
+#define BOX_STR_(x) #x
+#define BOX_STR(x) BOX_STR_(x)
+static_assert(TSDF_BOX_MAX_VOXELS == 268435456, "the exception text below says 2^28");
+// The voxel box of a cube -- the voxels whose centres it holds -- within the box limits (TSDF_BOX_MAX_DIM,
+// TSDF_BOX_MAX_VOXELS), or std::invalid_argument in `who`'s name. Returns the number of voxels.
+size_t cube_box(const BoundingCube<float>& volumn, float voxel_size, const char* who, int32_t origin[3], int32_t dims[3]) {
+  const double lo[3] = {volumn.xmin, volumn.ymin, volumn.zmin}, hi[3] = {volumn.xmax, volumn.ymax, volumn.zmax};
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    const double v0 = std::ceil(lo[a] / (double)voxel_size), v1 = std::floor(hi[a] / (double)voxel_size);
+    if (!(v0 <= v1) || !(v0 > -1e9) || !(v1 < 1e9) || v1 - v0 >= (double)TSDF_BOX_MAX_DIM)
+      throw std::invalid_argument(std::string(who) + ": the cube holds no voxel centre, or more than "
+                                  BOX_STR(TSDF_BOX_MAX_DIM) " along an axis");
+    origin[a] = (int32_t)v0;
+    dims[a] = (int32_t)(v1 - v0) + 1;
+    n *= (size_t)dims[a];
+  }
+  if (n > (size_t)TSDF_BOX_MAX_VOXELS) throw std::invalid_argument(std::string(who) + ": more than 2^28 voxels");
+  return n;
+}
+#undef BOX_STR
+#undef BOX_STR_
+}  // namespace
+
 struct DistanceField TSDFGrid::DistanceField(const BoundingCube<float>& volumn, int max_dist, int min_weight,
                                              bool unknown) {
   if (group_) throw std::runtime_error("TSDFGrid::DistanceField: not available on a sharded volume");
-  const double lo[3] = {volumn.xmin, volumn.ymin, volumn.zmin}, hi[3] = {volumn.xmax, volumn.ymax, volumn.zmax};
   struct DistanceField f;
   tsdf_edt_config c;
   tsdf_edt_config_default(&c);
-  size_t n = 1;
-  for (int a = 0; a < 3; ++a) {
-    const double v0 = std::ceil(lo[a] / (double)voxel_size_), v1 = std::floor(hi[a] / (double)voxel_size_);
-    if (!(v0 <= v1) || !(v0 > -1e9) || !(v1 < 1e9) || v1 - v0 >= 2048.0)
-      throw std::invalid_argument("TSDFGrid::DistanceField: the cube holds no voxel centre, or more than 2048 along an axis");
-    c.origin[a] = f.origin[a] = (int32_t)v0;
-    c.dims[a] = f.dims[a] = (int32_t)(v1 - v0) + 1;
-    n *= (size_t)c.dims[a];
-  }
-  if (n > ((size_t)1 << 28)) throw std::invalid_argument("TSDFGrid::DistanceField: more than 2^28 voxels");
+  const size_t n = cube_box(volumn, voxel_size_, "TSDFGrid::DistanceField", f.origin, f.dims);
+  for (int a = 0; a < 3; ++a) c.origin[a] = f.origin[a], c.dims[a] = f.dims[a];
   c.max_dist = f.max_dist = max_dist;
   c.min_weight = min_weight;
   c.sites = TSDF_EDT_SURFACE | (unknown ? TSDF_EDT_UNKNOWN : 0);
@@ -319,18 +335,9 @@ std::vector<std::vector<int32_t>> TSDFGrid::TravelPaths(const struct TravelField
 }
 
 FreeLayer TSDFGrid::MakeFreeLayer(const BoundingCube<float>& volumn) const {
-  const double lo[3] = {volumn.xmin, volumn.ymin, volumn.zmin}, hi[3] = {volumn.xmax, volumn.ymax, volumn.zmax};
-  FreeLayer l;
-  for (int a = 0; a < 3; ++a) {  // (DistanceField's box of the same cube)
-    const double v0 = std::ceil(lo[a] / (double)voxel_size_), v1 = std::floor(hi[a] / (double)voxel_size_);
-    if (!(v0 <= v1) || !(v0 > -1e9) || !(v1 < 1e9) || v1 - v0 >= 2048.0)
-      throw std::invalid_argument("TSDFGrid::MakeFreeLayer: the cube holds no voxel centre, or more than 2048 along an axis");
-    l.origin[a] = (int32_t)v0;
-    l.dims[a] = (int32_t)(v1 - v0) + 1;
-  }
-  const int64_t words = tsdf_free_words(l.dims);
-  if (words == 0) throw std::invalid_argument("TSDFGrid::MakeFreeLayer: more than 2^28 voxels");
-  l.bits.assign((size_t)words, 0u);
+  FreeLayer l;  // (DistanceField's box of the same cube)
+  cube_box(volumn, voxel_size_, "TSDFGrid::MakeFreeLayer", l.origin, l.dims);
+  l.bits.assign((size_t)tsdf_free_words(l.dims), 0u);
   return l;
 }
 

@@ -966,6 +966,52 @@ class Engine:
         return (SE3((p.qx, p.qy, p.qz, p.qw), (p.tx, p.ty, p.tz)),
                 dict(status=int(r.status), iterations=int(r.iterations), inliers=int(r.inliers), rmse=float(r.rmse)))
 
+    # ---- what the array calls below share (surface_normals .. view_gain) ----
+    @staticmethod
+    def _kind(device):
+        return TSDF_MEM_DEVICE if device else TSDF_MEM_HOST
+
+    def _alloc(self, shape, dtype, device, zero=False):
+        """An empty (zero=True: zeroed) array of a numpy dtype: numpy for a host call, a torch tensor on this
+        engine's GPU for a device call."""
+        if device:
+            import torch
+            return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, np.dtype(dtype).name),
+                                                          device=f"cuda:{self.device}")
+        return (np.zeros if zero else np.empty)(shape, dtype)
+
+    @staticmethod
+    def _box(origin, dims, who=""):
+        """(o, d, shape) of a box: origin (None: a call that takes dims alone) and dims as lists of three ints,
+        and the shape (nz, ny, nx) of its arrays. `who` opens the error text."""
+        d = [int(v) for v in dims]
+        o = None if origin is None else [int(v) for v in origin]
+        if len(d) != 3 or (o is not None and len(o) != 3):
+            raise ValueError(who + ("dims are three integers" if o is None else
+                                    "origin and dims are three integers each"))
+        return o, d, (d[2], d[1], d[0])
+
+    @staticmethod
+    def _box_ok(d):
+        """The library's box limits (TSDF_BOX_MAX_DIM, TSDF_BOX_MAX_VOXELS)."""
+        return all(1 <= v <= _lib.TSDF_BOX_MAX_DIM for v in d) and d[0] * d[1] * d[2] <= _lib.TSDF_BOX_MAX_VOXELS
+
+    @staticmethod
+    def _same_box(a, o, d):
+        """Whether the dict `a` (a travel field, a layer) lies over the box o, d."""
+        return [int(v) for v in a["dims"]] == list(d) and [int(v) for v in a["origin"]] == list(o)
+
+    def _call(self, name, tensors, fn, *args, allow=()):
+        """fn(handle, *args) between the two orderings with torch's stream for `tensors` (None entries are
+        skipped): wait, call, signal, then check -- a failed call has signalled before it raises. Returns the
+        code, which is TSDF_OK or one of `allow`."""
+        self._wait_torch(*tensors)
+        rc = fn(self._h, *args)
+        self._signal_torch(*tensors)
+        if rc not in allow:
+            _lib.check(rc, name)
+        return rc
+
     # ---- UV dose ----
     def _points(self, a, device, cols=3):
         """An (n, cols) f32 array as the call takes it (cols=1: (n,); cols=None: any 2-D matrix): a
@@ -992,16 +1038,9 @@ class Engine:
         sample_offset 0.5 for mesh vertices (the mesh's half-voxel shift), 0 for raycast_surface points.
         numpy in and out, or with device=True torch tensors on this engine's GPU."""
         p = self._points(points, device)
-        if device:
-            import torch
-            out = torch.empty_like(p)
-        else:
-            out = np.zeros_like(p)
-        self._wait_torch(p, out)
-        _lib.check(_lib.load().tsdf_surface_normals(self._h, _ptr(p), p.shape[0], float(sample_offset), _ptr(out),
-                                                    TSDF_MEM_DEVICE if device else TSDF_MEM_HOST),
-                   "tsdf_surface_normals")
-        self._signal_torch(p, out)
+        out = self._alloc(tuple(p.shape), np.float32, device, zero=not device)
+        self._call("tsdf_surface_normals", (p, out), _lib.load().tsdf_surface_normals, _ptr(p), p.shape[0],
+                   float(sample_offset), _ptr(out), self._kind(device))
         return out
 
     def uv_dose(self, points, normals, emitters, dose=None, device: bool = False, **cfg):
@@ -1012,33 +1051,20 @@ class Engine:
         zeros; a given array or tensor of the right kind is updated in place). Keywords are
         tsdf_uv_config's fields (bias, step, min_range, max_range, sample_offset, min_weight, use_grid).
         Returns the dose array, or with device=True the tensor."""
-        L = _lib.load()
-        c = self._uv_config("uv_dose", cfg)
-        p = self._points(points, device)
-        nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
-        em = np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
+        c, p, nr, em = self._uv_inputs("uv_dose", points, normals, emitters, device, cfg)
         n = p.shape[0]
-        if dose is None:
-            if device:
-                import torch
-                d = torch.zeros((n,), dtype=torch.float32, device=p.device)
-            else:
-                d = np.zeros(n, np.float32)
-        else:
-            d = self._points(dose, device, cols=1)
+        d = self._alloc((n,), np.float32, device, zero=True) if dose is None else self._points(dose, device, cols=1)
         if tuple(nr.shape) != tuple(p.shape) or d.shape[0] != n:
             raise ValueError("points, normals and dose do not match")
-        self._wait_torch(p, nr, d)
-        rc = L.tsdf_uv_dose(self._h, _ptr(p), _ptr(nr), n, _ptr(em), em.shape[0], C.byref(c), _ptr(d),
-                            TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
-        self._signal_torch(p, nr, d)
-        _lib.check(rc, "tsdf_uv_dose")
+        self._call("tsdf_uv_dose", (p, nr, d), _lib.load().tsdf_uv_dose, _ptr(p), _ptr(nr), n, _ptr(em), em.shape[0],
+                   C.byref(c), _ptr(d), self._kind(device))
         return d
 
-    def _uv_config(self, what, cfg):
-        L = _lib.load()
+    def _uv_inputs(self, what, points, normals, emitters, device, cfg):
+        """What uv_dose and uv_irradiance share: (tsdf_uv_config from the keywords, points, normals -- the
+        surface's own when None -- and the emitters as (m, 4) f32 on the host)."""
         c = _lib.UvConfig()
-        L.tsdf_uv_config_default(self._h, C.byref(c))
+        _lib.load().tsdf_uv_config_default(self._h, C.byref(c))
         for k, v in cfg.items():
             if k in ("min_weight", "use_grid"):
                 setattr(c, k, int(v))
@@ -1046,7 +1072,9 @@ class Engine:
                 setattr(c, k, float(v))
             else:
                 raise TypeError(f"{what}: unknown option {k}")
-        return c
+        p = self._points(points, device)
+        nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
+        return c, p, nr, np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
 
     # ---- lamp-stop planning ----
     def uv_irradiance(self, points, normals, emitters, first, device: bool = False, **cfg):
@@ -1056,11 +1084,7 @@ class Engine:
         (m, 4) f32 and first (C + 1,) int32 on the host (uv.tube_candidates), first[0] == 0, non-decreasing,
         first[-1] == m. Keywords are tsdf_uv_config's fields, as uv_dose's. Returns (C, n) f32: a numpy
         array, or with device=True a tensor on this engine's GPU."""
-        L = _lib.load()
-        c = self._uv_config("uv_irradiance", cfg)
-        p = self._points(points, device)
-        nr = self.surface_normals(p, c.sample_offset, device) if normals is None else self._points(normals, device)
-        em = np.ascontiguousarray(emitters, dtype=np.float32).reshape(-1, 4)
+        c, p, nr, em = self._uv_inputs("uv_irradiance", points, normals, emitters, device, cfg)
         fi = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
         if tuple(nr.shape) != tuple(p.shape):
             raise ValueError("points and normals do not match")
@@ -1068,16 +1092,9 @@ class Engine:
             raise _lib.TSDFError("tsdf_uv_irradiance: invalid argument (first holds C + 1 offsets and ends at the "
                                  "number of emitters)")
         n, nc = p.shape[0], fi.size - 1
-        if device:
-            import torch
-            out = torch.empty((nc, n), dtype=torch.float32, device=p.device)
-        else:
-            out = np.empty((nc, n), np.float32)
-        self._wait_torch(p, nr, out)
-        rc = L.tsdf_uv_irradiance(self._h, _ptr(p), _ptr(nr), n, _ptr(em), _ptr(fi), nc, C.byref(c), _ptr(out),
-                                  TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
-        self._signal_torch(p, nr, out)
-        _lib.check(rc, "tsdf_uv_irradiance")
+        out = self._alloc((nc, n), np.float32, device)
+        self._call("tsdf_uv_irradiance", (p, nr, out), _lib.load().tsdf_uv_irradiance, _ptr(p), _ptr(nr), n, _ptr(em),
+                   _ptr(fi), nc, C.byref(c), _ptr(out), self._kind(device))
         return out
 
     def uv_plan(self, irradiance, need, weight=None, max_stops: int = 16, min_gain: float = 0.0,
@@ -1089,7 +1106,6 @@ class Engine:
         for all 1 (uv.vertex_area * prob). Deterministic: the same inputs give the same bits. Returns
         dict(stops (k,) int32, gains (k,) f64, need (n,) f32: what is still missing after the stops); need is
         a new array, or with device=True a new tensor (irradiance and need may be tensors then)."""
-        L = _lib.load()
         E = self._points(irradiance, device, cols=None)
         nc, n = int(E.shape[0]), int(E.shape[1])
         if device:
@@ -1104,12 +1120,8 @@ class Engine:
         c = _lib.UvPlanConfig(int(max_stops), float(min_gain))
         k = max(int(max_stops), 0)
         stops, gains, num = np.zeros(k, np.int32), np.zeros(k, np.float64), C.c_int32(0)
-        arrs = (E, nd) if w is None else (E, nd, w)
-        self._wait_torch(*arrs)
-        rc = L.tsdf_uv_plan(self._h, _ptr(E), nc, n, _ptr(nd), _ptr(w), C.byref(c), _ptr(stops), _ptr(gains),
-                            C.byref(num), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
-        self._signal_torch(*arrs)
-        _lib.check(rc, "tsdf_uv_plan")
+        self._call("tsdf_uv_plan", (E, nd, w), _lib.load().tsdf_uv_plan, _ptr(E), nc, n, _ptr(nd), _ptr(w), C.byref(c),
+                   _ptr(stops), _ptr(gains), C.byref(num), self._kind(device))
         return dict(stops=stops[:num.value].copy(), gains=gains[:num.value].copy(), need=nd)
 
     # ---- distance field ----
@@ -1127,29 +1139,16 @@ class Engine:
         L = _lib.load()
         c = _lib.EdtConfig()
         L.tsdf_edt_config_default(C.byref(c))
-        o, d = [int(v) for v in origin], [int(v) for v in dims]
-        if len(o) != 3 or len(d) != 3:
-            raise ValueError("origin and dims are three integers each")
+        o, d, shape = self._box(origin, dims)
         c.origin, c.dims = (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d)
         c.max_dist, c.min_weight = int(max_dist), int(min_weight)
         c.sites = _lib.TSDF_EDT_SURFACE | (_lib.TSDF_EDT_UNKNOWN if unknown else 0)
-        # (a refused box allocates nothing: one element stands in for the outputs)
-        ok = all(1 <= v <= 2048 for v in d) and d[0] * d[1] * d[2] <= 1 << 28
-        shape = (d[2], d[1], d[0]) if ok else (1,)
-        if device:
-            import torch
-            dev = f"cuda:{self.device}"
-            d2 = torch.empty(shape, dtype=torch.uint16, device=dev)
-            st = torch.empty(shape, dtype=torch.uint8, device=dev) if state else None
-        else:
-            d2 = np.empty(shape, np.uint16)
-            st = np.empty(shape, np.uint8) if state else None
-        out = _lib.EdtOut(_ptr(d2), _ptr(st), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
-        outs = (d2,) if st is None else (d2, st)
-        self._wait_torch(*outs)
-        rc = L.tsdf_distance_field(self._h, C.byref(c), C.byref(out))
-        self._signal_torch(*outs)
-        _lib.check(rc, "tsdf_distance_field")
+        if not self._box_ok(d):  # (a refused box allocates nothing: one element stands in for the outputs)
+            shape = (1,)
+        d2 = self._alloc(shape, np.uint16, device)
+        st = self._alloc(shape, np.uint8, device) if state else None
+        out = _lib.EdtOut(_ptr(d2), _ptr(st), self._kind(device))
+        self._call("tsdf_distance_field", (d2, st), L.tsdf_distance_field, C.byref(c), C.byref(out))
         return dict(d2=d2, state=st, origin=tuple(o), dims=tuple(d), max_dist=int(max_dist), unknown=bool(unknown))
 
     # ---- travel field ----
@@ -1189,9 +1188,7 @@ class Engine:
         L = _lib.load()
         if field.get("state") is None:
             raise ValueError("travel_field: the field has no state (distance_field(..., state=True))")
-        d = [int(v) for v in field["dims"]]
-        o = [int(v) for v in field["origin"]]
-        shape = (d[2], d[1], d[0])
+        o, d, shape = self._box(field["origin"], field["dims"], "travel_field: ")
         d2 = self._box_array(field["d2"], np.uint16, shape, device, "d2")
         st = self._box_array(field["state"], np.uint8, shape, device, "state")
         s = np.ascontiguousarray(np.asarray(seeds, np.int64).reshape(-1, 3) - np.asarray(o, np.int64))
@@ -1200,18 +1197,11 @@ class Engine:
         L.tsdf_travel_config_default(C.byref(c))
         c.dims = (C.c_int32 * 3)(*d)
         c.clearance2, c.unknown_free = int(clearance2), 1 if unknown_free else 0
-        if device:
-            import torch
-            cost = torch.empty(shape, dtype=torch.uint32, device=f"cuda:{self.device}")
-        else:
-            cost = np.empty(shape, np.uint32)
+        cost = self._alloc(shape, np.uint32, device)
         seeded, rounds = C.c_int32(0), C.c_int32(0)
-        self._wait_torch(d2, st, cost)
-        rc = L.tsdf_travel_field(self._h, C.byref(c), _ptr(d2), _ptr(st), _ptr(s) if s.shape[0] else None,
-                                 int(s.shape[0]), _ptr(cost), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST,
-                                 C.byref(seeded), C.byref(rounds))
-        self._signal_torch(d2, st, cost)
-        _lib.check(rc, "tsdf_travel_field")
+        self._call("tsdf_travel_field", (d2, st, cost), L.tsdf_travel_field, C.byref(c), _ptr(d2), _ptr(st),
+                   _ptr(s) if s.shape[0] else None, int(s.shape[0]), _ptr(cost), self._kind(device), C.byref(seeded),
+                   C.byref(rounds))
         return dict(cost=cost, origin=tuple(o), dims=tuple(d), seeded=seeded.value, rounds=rounds.value)
 
     def travel_paths(self, travel, targets, max_len: int = 4096):
@@ -1222,14 +1212,14 @@ class Engine:
         longer max_len when a path was truncated. A field this library did not write may have no
         predecessor somewhere: ValueError."""
         L = _lib.load()
-        d = [int(v) for v in travel["dims"]]
+        _, d, shape = self._box(None, travel["dims"], "travel_paths: ")
         cost = travel["cost"]
         device = _is_torch_cuda(cost)
         if not device:
             cost = np.ascontiguousarray(cost, dtype=np.uint32)
         elif not cost.is_contiguous():
             cost = cost.contiguous()
-        if tuple(cost.shape) != (d[2], d[1], d[0]):
+        if tuple(cost.shape) != shape:
             raise ValueError("travel_paths: cost does not match dims")
         t = np.asarray(targets, np.int64).reshape(-1, 3) - np.asarray(travel["origin"], np.int64)
         t = np.ascontiguousarray(np.clip(t, -(1 << 30), 1 << 30).astype(np.int32))
@@ -1243,11 +1233,8 @@ class Engine:
             n = min(nt - k0, max((1 << 28) // max_len, 1))  # (a call takes T * max_len <= 2^28)
             tk = np.ascontiguousarray(t[k0:k0 + n])
             path, ln = np.zeros((n, max_len), np.int32), np.zeros(n, np.int32)
-            self._wait_torch(cost)
-            rc = L.tsdf_travel_paths(self._h, dims, _ptr(cost), TSDF_MEM_DEVICE if device else TSDF_MEM_HOST,
-                                     _ptr(tk), n, max_len, _ptr(path), _ptr(ln))
-            self._signal_torch(cost)
-            _lib.check(rc, "tsdf_travel_paths")
+            self._call("tsdf_travel_paths", (cost,), L.tsdf_travel_paths, dims, _ptr(cost), self._kind(device), _ptr(tk),
+                       n, max_len, _ptr(path), _ptr(ln))
             if (ln < 0).any():
                 raise ValueError("travel_paths: the field has a voxel without a predecessor (not a travel_field result)")
             if int(ln.max()) > max_len:  # (a path visits a voxel once: at most 2^28, one target per call then)
@@ -1260,9 +1247,7 @@ class Engine:
     # ---- observed free space ----
     def _free_box(self, layer):
         """(tsdf_free_box, the layer's words as the calls take them, whether they are device memory)."""
-        o, d = [int(v) for v in layer["origin"]], [int(v) for v in layer["dims"]]
-        if len(o) != 3 or len(d) != 3:
-            raise ValueError("a layer's origin and dims are three integers each")
+        o, d, _ = self._box(layer["origin"], layer["dims"], "a layer's ")
         bits = layer["bits"]
         device = _is_torch_cuda(bits)
         if device:
@@ -1299,13 +1284,8 @@ class Engine:
         if dp.ndim != 2:
             raise ValueError("free_observe: depth is (H, W)")
         h, w = int(dp.shape[0]), int(dp.shape[1])
-        Kc = K._c() if isinstance(K, CameraIntrinsics) else _lib.Intrinsics(*[float(v) for v in K])
-        self._wait_torch(bits, dp)
-        rc = L.tsdf_free_observe(self._h, C.byref(box), _ptr(bits), _ptr(dp), w, h,
-                                 TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(Kc),
-                                 C.byref(cam_T_world._c()), float(max_depth))
-        self._signal_torch(bits, dp)
-        _lib.check(rc, "tsdf_free_observe")
+        self._call("tsdf_free_observe", (bits, dp), L.tsdf_free_observe, C.byref(box), _ptr(bits), _ptr(dp), w, h,
+                   self._kind(device), C.byref(self._Kc(K)), C.byref(cam_T_world._c()), float(max_depth))
         return layer
 
     def free_apply(self, layer, field, count: bool = True):
@@ -1319,15 +1299,12 @@ class Engine:
         box, bits, device = self._free_box(layer)
         if field.get("state") is None:
             raise ValueError("free_apply: the field has no state (distance_field(..., state=True))")
-        o, d = [int(v) for v in field["origin"]], [int(v) for v in field["dims"]]
-        st = self._box_array(field["state"], np.uint8, (d[2], d[1], d[0]), device, "state")
+        o, d, shape = self._box(field["origin"], field["dims"], "free_apply: ")
+        st = self._box_array(field["state"], np.uint8, shape, device, "state")
         st = st.clone() if device else st.copy()
         n = C.c_int64(0)
-        self._wait_torch(bits, st)
-        rc = L.tsdf_free_apply(self._h, C.byref(box), _ptr(bits), (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d), _ptr(st),
-                               TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(n) if count else None)
-        self._signal_torch(bits, st)
-        _lib.check(rc, "tsdf_free_apply")
+        self._call("tsdf_free_apply", (bits, st), L.tsdf_free_apply, C.byref(box), _ptr(bits), (C.c_int32 * 3)(*o),
+                   (C.c_int32 * 3)(*d), _ptr(st), self._kind(device), C.byref(n) if count else None)
         return dict(field, state=st, promoted=int(n.value) if count else None)
 
     # ---- frontiers and components ----
@@ -1342,24 +1319,15 @@ class Engine:
         L = _lib.load()
         if field.get("state") is None:
             raise ValueError("frontier_mask: the field has no state (distance_field(..., state=True))")
-        o, d = [int(v) for v in field["origin"]], [int(v) for v in field["dims"]]
-        shape = (d[2], d[1], d[0])
-        if travel is not None and (tuple(int(v) for v in travel["dims"]) != tuple(d) or
-                                   tuple(int(v) for v in travel["origin"]) != tuple(o)):
+        o, d, shape = self._box(field["origin"], field["dims"], "frontier_mask: ")
+        if travel is not None and not self._same_box(travel, o, d):
             raise ValueError("frontier_mask: the travel field's box is not the distance field's")
         st = self._box_array(field["state"], np.uint8, shape, device, "state")
         cost = None if travel is None else self._box_array(travel["cost"], np.uint32, shape, device, "cost")
-        if device:
-            import torch
-            mask = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
-        else:
-            mask = np.empty(shape, np.uint8)
+        mask = self._alloc(shape, np.uint8, device)
         n = C.c_int64(0)
-        self._wait_torch(st, cost, mask)
-        rc = L.tsdf_frontier_mark(self._h, (C.c_int32 * 3)(*d), _ptr(st), _ptr(cost), _ptr(mask),
-                                  TSDF_MEM_DEVICE if device else TSDF_MEM_HOST, C.byref(n) if count else None)
-        self._signal_torch(st, cost, mask)
-        _lib.check(rc, "tsdf_frontier_mark")
+        self._call("tsdf_frontier_mark", (st, cost, mask), L.tsdf_frontier_mark, (C.c_int32 * 3)(*d), _ptr(st),
+                   _ptr(cost), _ptr(mask), self._kind(device), C.byref(n) if count else None)
         return dict(mask=mask, marked=int(n.value) if count else None, origin=tuple(o), dims=tuple(d))
 
     def components(self, mask, dims, key=None, min_size: int = 1, device: bool = False):
@@ -1372,35 +1340,26 @@ class Engine:
         without key; count = len(clusters); total: all components). label is numpy, or with device=True a
         torch tensor on this engine's GPU. Does not touch the volume."""
         L = _lib.load()
-        d = [int(v) for v in dims]
-        if len(d) != 3:
-            raise ValueError("dims are three integers")
-        ok = all(1 <= v <= 2048 for v in d) and d[0] * d[1] * d[2] <= 1 << 28
-        shape = (d[2], d[1], d[0]) if ok else tuple(np.shape(mask))
+        _, d, shape = self._box(None, dims)
+        if not self._box_ok(d):  # (a refused box: the arrays keep the mask's shape and the library says why)
+            shape = tuple(np.shape(mask))
         m = self._box_array(mask, np.uint8, shape, device, "mask")
         k = None if key is None else self._box_array(key, np.uint32, shape, device, "key")
-        if device:
-            import torch
-            label = torch.empty(shape, dtype=torch.uint32, device=f"cuda:{self.device}")
-        else:
-            label = np.empty(shape, np.uint32)
+        label = self._alloc(shape, np.uint32, device)
         c = _lib.ComponentsConfig()
         L.tsdf_components_config_default(C.byref(c))
         c.dims, c.min_size = (C.c_int32 * 3)(*d), int(min_size)
-        kind = TSDF_MEM_DEVICE if device else TSDF_MEM_HOST
         count, total = C.c_int32(0), C.c_int32(0)
-        self._wait_torch(m, k, label)
         # the two-call pattern with a first guess: a table too small asks again with the count it was told
         cap = 4096
-        for attempt in range(2):
+        for retry in ((_lib.TSDF_ERR_CAPACITY,), ()):
             clusters = np.zeros(cap, COMPONENT_DTYPE)
-            rc = L.tsdf_components(self._h, C.byref(c), _ptr(m), _ptr(k), _ptr(label), kind, _ptr(clusters), cap,
-                                   C.byref(count), C.byref(total))
+            rc = self._call("tsdf_components", (m, k, label), L.tsdf_components, C.byref(c), _ptr(m), _ptr(k),
+                            _ptr(label), self._kind(device), _ptr(clusters), cap, C.byref(count), C.byref(total),
+                            allow=retry)
             if rc != _lib.TSDF_ERR_CAPACITY:
                 break
             cap = int(count.value)
-        self._signal_torch(m, k, label)
-        _lib.check(rc, "tsdf_components")
         return dict(label=label, clusters=clusters[:count.value].copy(), count=int(count.value),
                     total=int(total.value))
 
@@ -1435,13 +1394,11 @@ class Engine:
             state, origin, dims = field_or_state["state"], field_or_state["origin"], field_or_state["dims"]
         else:
             state, origin, dims = field_or_state
-        o, d = [int(v) for v in origin], [int(v) for v in dims]
-        if len(o) != 3 or len(d) != 3:
-            raise ValueError("view_gain: origin and dims are three integers each")
-        st = self._box_array(state, np.uint8, (d[2], d[1], d[0]), device, "state")
+        o, d, shape = self._box(origin, dims, "view_gain: ")
+        st = self._box_array(state, np.uint8, shape, device, "state")
         bits = None
         if seen is not None:
-            if tuple(int(v) for v in seen["dims"]) != tuple(d) or tuple(int(v) for v in seen["origin"]) != tuple(o):
+            if not self._same_box(seen, o, d):
                 raise ValueError("view_gain: the seen layer's box is not the state's")
             bits = seen["bits"]
             wshape = (d[2], d[1], (d[0] + 31) // 32)
@@ -1464,7 +1421,7 @@ class Engine:
         L.tsdf_view_config_default(self._h, C.byref(c))
         c.origin, c.dims = (C.c_int32 * 3)(*o), (C.c_int32 * 3)(*d)
         c.width, c.height = w, h
-        c.K = K._c() if isinstance(K, CameraIntrinsics) else _lib.Intrinsics(*[float(v) for v in K])
+        c.K = self._Kc(K)
         c.far = float(far)
         c.miss_depth = float(far) if miss_depth is None else float(miss_depth)
         if step is not None:
@@ -1473,19 +1430,9 @@ class Engine:
             c.margin = float(margin)
         poses = (_lib.Pose * max(nv, 1))(*[v._c() for v in views])
         gain = np.zeros(nv, np.int64)
-        out = None
-        if depth:
-            shape = (nv, max(h, 0), max(w, 0))
-            if device:
-                import torch
-                out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}")
-            else:
-                out = np.empty(shape, np.float32)
-        self._wait_torch(st, bits, out)
-        rc = L.tsdf_view_gain(self._h, C.byref(c), _ptr(st), _ptr(bits), C.cast(poses, C.c_void_p), nv, _ptr(gain),
-                              _ptr(out) if nv else None, TSDF_MEM_DEVICE if device else TSDF_MEM_HOST)
-        self._signal_torch(st, bits, out)
-        _lib.check(rc, "tsdf_view_gain")
+        out = self._alloc((nv, max(h, 0), max(w, 0)), np.float32, device) if depth else None
+        self._call("tsdf_view_gain", (st, bits, out), L.tsdf_view_gain, C.byref(c), _ptr(st), _ptr(bits),
+                   C.cast(poses, C.c_void_p), nv, _ptr(gain), _ptr(out) if nv else None, self._kind(device))
         return dict(gain=gain, depth=out, origin=tuple(o), dims=tuple(d))
 
     def query(self, bounds=None) -> np.ndarray:

@@ -15,6 +15,8 @@ TSDF_OK = 0
 TSDF_ERR_CAPACITY = 4
 TSDF_MEM_HOST = 0
 TSDF_MEM_DEVICE = 1
+TSDF_BOX_MAX_DIM = 2048
+TSDF_BOX_MAX_VOXELS = 1 << 28
 STATUS_POOL_EXHAUSTED = 1
 STATUS_NEWKEY_OVERFLOW = 2
 STATUS_DDA_OVERFLOW = 4

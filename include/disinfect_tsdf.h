@@ -635,6 +635,13 @@ int tsdf_uv_plan(tsdf_engine* e, const float* irradiance /* C x n */, int32_t C,
                  const tsdf_uv_plan_config* cfg /* NULL = defaults */, int32_t* stops /* host, max_stops */,
                  double* gains /* host, max_stops */, int32_t* num_stops /* host */, int mem_kind);
 
+/* ---- Box calls: the limits of every box of voxels the calls below take ----
+ * A box is dims = (nx, ny, nz) voxels, with an origin in global voxel coordinates where a call reads the volume
+ * or a layer. Every box call requires each dims[i] in 1 .. TSDF_BOX_MAX_DIM and nx * ny * nz <=
+ * TSDF_BOX_MAX_VOXELS: "the box limits" below. */
+#define TSDF_BOX_MAX_DIM 2048
+#define TSDF_BOX_MAX_VOXELS ((int64_t)1 << 28)
+
 /* ---- Euclidean distance field over a box of the volume (no reference counterpart) ----
  * The exact squared Euclidean distance, in voxels, from every voxel of a box to the nearest surface
  * voxel of the volume -- the layer a planner asks for clearance, which the TSDF only knows inside its
@@ -651,7 +658,7 @@ int tsdf_uv_plan(tsdf_engine* e, const float* irradiance /* C x n */, int32_t C,
  * sites gives R * R everywhere. Only sites inside the box count, so a voxel at least R voxels from every
  * face of the box holds the volume's true saturated distance: a caller pads its region by R. d2 at a
  * free voxel is the clearance, at an inside voxel the penetration depth; state gives the sign.
- * Required: each dims[i] in 1 .. 2048, nx * ny * nz <= 2^28, every voxel of the box grown by one voxel
+ * Required: the box limits (TSDF_BOX_MAX_DIM, TSDF_BOX_MAX_VOXELS), every voxel of the box grown by one voxel
  * inside the int16 block range, max_dist in 1 .. 255, min_weight >= 0, sites one of the two values, d2
  * non-NULL; anything else is TSDF_ERR_INVALID_ARG with nothing written. The call completes a pending
  * pipelined frame first, runs asynchronously on the engine stream for device memory and copies and
@@ -699,7 +706,7 @@ int tsdf_distance_field(tsdf_engine* e, const tsdf_edt_config* cfg, const tsdf_e
  * and their clearance margin are not. The volume only holds blocks near surfaces, so the open interior of a
  * room is state 0 and a field with unknown_free = 0 is confined to the thin observed-free shell around the
  * surfaces. With unknown_free = 1 an unobserved gap in a wall leaks: the field passes through it.
- * Required: e, cfg, d2, state and cost non-NULL, each dims[i] in 1 .. 2048, nx * ny * nz <= 2^28,
+ * Required: e, cfg, d2, state and cost non-NULL, the box limits (TSDF_BOX_MAX_DIM, TSDF_BOX_MAX_VOXELS),
  * clearance2 in 0 .. 65025, unknown_free 0 or 1, mem_kind one of the two, S >= 0 and seeds non-NULL when
  * S > 0; anything else is TSDF_ERR_INVALID_ARG with nothing written. d2, state and cost are mem_kind memory
  * alike (host: the call copies up and down; device: it runs on the engine stream); seeds, seeded and rounds
@@ -777,9 +784,10 @@ int tsdf_travel_paths(tsdf_engine* e, const int32_t dims[3], const uint32_t* cos
  * for every voxel v of the state array's box (origin, dims; nz * ny * nx bytes, x fastest: a distance
  * field's). States 1 and 2, and voxels outside the layer's box, stay as they are: an inside voxel is never
  * promoted. The two boxes may overlap partly, nest or be disjoint. *promoted is the number of voxels changed.
- * Required, of the layer's box and of apply's state box alike: each dims[i] in 1 .. 2048, nx * ny * nz <=
- * 2^28, every voxel in a block of the int16 block range (origin >> 3 >= -32768, (origin + dims - 1) >> 3 <=
- * 32767); width / height in 1 .. the engine's max_width / max_height; max_depth > 0; mem_kind one of the
+ * Required, of the layer's box and of apply's state box alike: the box limits (TSDF_BOX_MAX_DIM,
+ * TSDF_BOX_MAX_VOXELS), every voxel in a block of the int16 block range (origin >> 3 >= -32768,
+ * (origin + dims - 1) >> 3 <= 32767); width / height in 1 .. the engine's max_width / max_height;
+ * max_depth > 0; mem_kind one of the
  * two; every pointer non-NULL except promoted. Anything else is TSDF_ERR_INVALID_ARG with nothing written.
  * Neither call touches the volume: the engine lends its stream and scratch (grown on demand, freed by
  * tsdf_destroy), no status bits are set, pending pipelined frames stay pending -- the natural use is one
@@ -804,7 +812,8 @@ int tsdf_free_apply(tsdf_engine* e, const tsdf_free_box* box, const uint32_t* bi
  * Where the map ends, as a short list of places to look from. A frontier is an observed-free, reachable voxel
  * that touches unobserved space; tsdf_components clusters any voxel mask into its 26-connected components and
  * reports each one's size, place and cheapest member. All integers, so the results are exact. Boxes as
- * everywhere: dims = (nx, ny, nz), each in 1 .. 2048, nx * ny * nz <= 2^28, arrays nz * ny * nx with x fastest,
+ * everywhere: dims = (nx, ny, nz) within the box limits (TSDF_BOX_MAX_DIM, TSDF_BOX_MAX_VOXELS), arrays
+ * nz * ny * nx with x fastest,
  * linear index (z * ny + y) * nx + x.
  *
  * tsdf_frontier_mark: mask[v] = 1 when all three hold, else 0:
@@ -895,7 +904,8 @@ int tsdf_components(tsdf_engine* e, const tsdf_components_config* cfg, const uin
  * voxels that views already chosen will observe. To commit view i a caller ORs it in with
  * tsdf_free_observe(seen, depth_out + i W H, ...): with margin == truncation and max_depth >= 2 far the new
  * bits on state-0 voxels then number exactly gain[i].
- * Required: dims each in 1 .. 2048, nx ny nz <= 2^28, the box inside the int16 block range; width / height in
+ * Required: the box limits (TSDF_BOX_MAX_DIM, TSDF_BOX_MAX_VOXELS), the box inside the int16 block range;
+ * width / height in
  * 1 .. the engine's max_width / max_height; V in 0 .. 4096 and V W H <= 2^26; far > 0, step > 0, margin >= 0,
  * miss_depth 0 or in (0, far], all finite; mem_kind one of the two; e, cfg and state non-NULL, views and gain
  * non-NULL when V > 0. Anything else is TSDF_ERR_INVALID_ARG with nothing written. V == 0 returns TSDF_OK.
