@@ -360,7 +360,7 @@ __device__ __forceinline__ void update_issue(const UpdConst& C, const VisRec& r,
   update_issue_pix<Raw>(C, r, lane, hf, S);
 }
 
-template <bool Raw>
+template <bool Raw, bool Lanes>
 __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r, int lane, int hf, UpdState& S,
                                               float& mn, int& my_upd) {
   const int off = (hf * 256 + lane * 4) * 4;
@@ -494,12 +494,19 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
       setc(pr, j, pn);
     }
   }
-  if (upd_mask == 0xF || fresh) {
-    // all four voxels written (a fresh block's untouched voxels get AquireBlock's state)
+  if (Lanes ? upd_mask || fresh : upd_mask == 0xF || fresh) {
+    // Lanes (every form but C5's k_integrate_vg): the lane's whole 16-B vectors, whenever one of its four voxels was updated (a fresh block: always,
+    // its untouched voxels get AquireBlock's state). An untouched voxel's registers still hold the bits
+    // that were loaded -- ts and cw change only under a0 / a1, pr only under upd_mask -- and this lane is
+    // the only writer of these 48 bytes during the launch, so writing them back
+    // changes nothing; a lane with no updated voxel stores nothing.
     pool_st(blk + off, ts);
     pool_st(blk + kProbOffset + off, pr);
     pool_stu(blk + kRgbwOffset + off, cw);
-  } else if (upd_mask) {  // only the updated voxels' words: writes stay N_upd x 12 B
+  } else if (upd_mask) {
+    // k_integrate_vg / k_integrate_vg_g, whose other workgroups build the view grid beside the update, keep the
+    // per-word form, only the updated voxels' words: whole lanes measured 0.3 us slower there (DESIGN.md 4,
+    // round 10)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (upd_mask & (1 << j)) {
@@ -511,12 +518,12 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
   my_upd += __popc(upd_mask);
 }
 
-template <bool Raw>
+template <bool Raw, bool Lanes>
 __device__ __forceinline__ void update_block(const UpdConst& C, const VisRec& r, int lane, int hf, float& mn,
                                              int& my_upd) {
   UpdState S;
   update_issue<Raw>(C, r, lane, hf, S);
-  update_finish<Raw>(C, r, lane, hf, S, mn, my_upd);
+  update_finish<Raw, Lanes>(C, r, lane, hf, S, mn, my_upd);
 }
 
 // The concatenated band lists: band i holds visible-block indices [start_i, start_i + count_i).
@@ -560,7 +567,8 @@ __device__ __forceinline__ size_t band_find(const EngineDev& D, int bst, int lan
 #endif
 // nint: the update's workgroups (the whole grid). L: the LDS of the last arriver's carving resolve.
 // returns true in the workgroup that arrived last (and ran the carving tail)
-template <bool Graph, bool Raw>
+// Lanes: update_finish's write-back form
+template <bool Graph, bool Raw, bool Lanes = true>
 __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FrameParams& Pv,
                                                const FrameArgs* __restrict__ A, int nint, DeleteLds& L,
                                                int narrive = 0, const ViewFuse* F = nullptr) {
@@ -615,7 +623,7 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
       } else {
         r = vis[band_find_n(nblocks, bst, lane, b)];
       }
-      update_block<Raw>(C, r, lane, hf, mn, my_upd);
+      update_block<Raw, Lanes>(C, r, lane, hf, mn, my_upd);
     }
     mn = wave_min_u(mn);
     if (lane == 0) s_min[wave] = mn;
@@ -709,7 +717,7 @@ __device__ __forceinline__ void integrate_vg(const EngineDev& D, const FramePara
   const ViewFuse F{R, V, vtag};
   const int narr = (int)gridDim.x;
   if ((int)blockIdx.x < nint) {
-    integrate_body<Graph, false>(D, Pv, A, nint, L, narr, &F);
+    integrate_body<Graph, false, false>(D, Pv, A, nint, L, narr, &F);
     return;
   }
   const int w = ((int)blockIdx.x - nint) * 256 + (int)threadIdx.x;  // (one occupancy word per thread)
@@ -1310,7 +1318,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     for (int k = pair; k < n; k += 2) {
       const VisRec r = s_list[k];
       float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
-      update_block<false>(C, r, lane, hf, mn, my_upd);
+      update_block<false, true>(C, r, lane, hf, mn, my_upd);
       mn = wave_min_u(mn);
       if (lane == 0) {
         s_pmin[2 * k + hf] = mn;
