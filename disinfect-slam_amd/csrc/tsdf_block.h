@@ -30,6 +30,16 @@ __device__ __forceinline__ int wave_sum(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// wave-wide sum as a wave-uniform value (every lane of the wave active): wave_min_u's DPP steps, no
+// permute addresses held in registers
+__device__ __forceinline__ int wave_sum_u(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);
+  return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+         __builtin_amdgcn_readlane(v, 48);
+}
 __device__ __forceinline__ int wave_incl_scan(int v) {
   const int l = lane_id();
 #pragma unroll

@@ -25,7 +25,7 @@ void set_error(const char* what) { g_last_error = what; }
 //   TSDF_PIPELINE=0               unpipelined frames: two launches per frame (k_ingest_dda, k_integrate)
 //   TSDF_PIPE_MAX_PIXELS=n        largest frame (pixels) that is pipelined (default 2^20: C4, 1280x720, is within it)
 //   TSDF_FRAME_ORDER=0..2         k_frame grid order of its parts (PipeArgs.order; default 2)
-//   TSDF_FRAME_UPD_WGS=n          (A/B) k_frame update workgroups in total (default kFrameUpdWgsPer4Cu / 4 = 2.75 per CU: 704)
+//   TSDF_FRAME_UPD_WGS=n          (A/B) k_frame update workgroups in total (default kFrameUpdWgsPer4Cu / 4 = 3 per CU: 768)
 //   TSDF_CAND_CAP=n               (tests) smaller carve-candidate list, to exercise its overflow
 //   TSDF_MESH_GRID=n              (tests) fewer k_mesh workgroups, to exercise its grid stride
 //   TSDF_FREE_CULL=0              (A/B, tests) tsdf_free_observe without its two culls (full words, bricks outside the frustum)
@@ -316,8 +316,11 @@ int tsdf_create(const tsdf_config* cfg_in, int device, tsdf_engine** out) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_pre, reinterpret_cast<const void*>(k_frame),
                                                      kIntegrateThreads, 0) != hipSuccess)
       return fail(TSDF_ERR_HIP);
-    // 2.75 update workgroups per CU by default (of 6 that fit): the other slots take the sweep's and
-    // the tile pairs' workgroups from the start. Round 7 (tile pairs, 600 tile workgroups at 640x480;
+    // 3 update workgroups per CU by default (of 7 that fit): the other slots take the sweep's and
+    // the tile pairs' workgroups from the start. Round 11 (7 waves per SIMD, 1,792 slots; same box,
+    // interleaved, 3 runs, driver command / 300 frames): 704 24.88-24.97k / 28.26-28.39k frames/s, 768
+    // 26.56-26.88k / 28.97-29.12k, 832 24.55-24.64k / 28.52-29.08k, 896 25.90-26.09k / 27.71-29.25k
+    // (profiles/ab/r11_upd_wgs_ab.txt). Round 7, at 6 waves and 2.75 per CU (tile pairs, 600 tile workgroups at 640x480;
     // same box, interleaved, driver command / 300 frames): 704 21.21-21.26k / 24.86-25.01k frames/s,
     // 640 20.69-20.91k / 24.42-24.68k, 608 20.39-20.55k / 24.40-24.48k (the parent, 1,200 tile workgroups
     // and 640: 20.93-21.13k / 23.29-23.52k; profiles/ab/r7_tile_pairs_ab.txt). Round 6, final build (exact semantic chain, 6 waves per

@@ -360,7 +360,46 @@ __device__ __forceinline__ void update_issue(const UpdConst& C, const VisRec& r,
   update_issue_pix<Raw>(C, r, lane, hf, S);
 }
 
-template <bool Raw, bool Lanes>
+// ---- pass 3 of the update: semantic fusion (voxel_tsdf.cu:196-202), the reference's float chain operation
+// for operation:
+//   P = expf((w_old logf(p) + w_new logf(ht)) / wc), N = expf((w_old logf(1 - p) + w_new logf(lt)) / wc),
+//   p' = P / (P + N)
+// (logf / expf: the oracle's fixed algorithms, sem_logf / sem_expf; the quotients IEEE-exact). The fast path
+// runs on both voxels of a pair; a voxel whose operands leave its range -- p 0 or 1, ht or lt 0, extreme
+// quotients -- is recomputed with every special case (sem_update_exact). Two forms, the same operations on the
+// same operands in both: the interleaved one at the end of update_finish (Pairs = false), and
+// sem_pair (update_finish<.., Pairs = true>): one pair, directly after its pass 2 and inside its a0 || a1
+// region; the result is kept only under a0 / a1. It reads what pass 2 still holds -- w_old, w_new, wc, the
+// pixel's logs, and the refined reciprocal of wc, which is div_pair's own y1 (div_refine(wc, iwc), operation
+// for operation) -- so nothing but the 12 state registers, the masks, mn and the other pair's pixels is live
+// across the pairs.
+__device__ __forceinline__ void sem_pair(float4& pr, int j0, int j1, bool a0, bool a1, bool pf0, bool pf1, v2f w_old,
+                                         v2f w_new, v2f wc, v2f iwc, v2f lnh, v2f lnl) {
+  const v2f pv = v2(comp(pr, j0), comp(pr, j1));
+  const v2f an = w_old * sem_log_fast2(pv) + w_new * lnh;
+  const v2f bn = w_old * sem_log_fast2(v2(1.0f, 1.0f) - pv) + w_new * lnl;
+  const v2f y1 = div_refine(wc, iwc);
+  const v2f sp = sem_exp_fast2(div_expand(an, wc, y1));
+  const v2f sn = sem_exp_fast2(div_expand(bn, wc, y1));
+  const v2f ss = sp + sn;
+  v2f pn = div_expand(sp, ss, div_refine(ss, v2(__builtin_amdgcn_rcpf(ss.x), __builtin_amdgcn_rcpf(ss.y))));
+  if (a0) {
+    if (__builtin_expect(!sem_voxel_fast(pf0, pv.x), 0))
+      pn.x = sem_update_exact(pv.x, w_old.x, w_new.x, wc.x, lnh.x, lnl.x);
+    setc(pr, j0, pn.x);
+  }
+  if (a1) {
+    if (__builtin_expect(!sem_voxel_fast(pf1, pv.y), 0))
+      pn.y = sem_update_exact(pv.y, w_old.y, w_new.y, wc.y, lnh.y, lnl.y);
+    setc(pr, j1, pn.y);
+  }
+}
+
+// Pairs: the lane's two voxel pairs go through passes 2 and 3 one after the other (k_frame / k_frame_g: the
+// form that fits 72 VGPRs, 7 waves per SIMD); otherwise pass 2 of both pairs, then pass 3 of both with their
+// chains interleaved (k_integrate_t, k_integrate_vg at 6 waves per SIMD). The same operations on the same
+// operands in both forms, so the same bits.
+template <bool Raw, bool Lanes, bool Pairs>
 __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r, int lane, int hf, UpdState& S,
                                               float& mn, int& my_upd) {
   const int off = (hf * 256 + lane * 4) * 4;
@@ -377,12 +416,14 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
   // ---- pass 2: tsdf_integrate_kernel's update (voxel_tsdf.cu:174-203) of tsdf, colour and weight,
   // branch-free on packed pairs; each voxel's result is kept only where it is updated (the
   // reference's conditions: in image, 0 < d <= max_depth, sdf > -trunc). The semantic update
-  // follows in pass 3, once the pixel records and the other state are dead (its chain of logs and
-  // exponentials beside them spilled the loop out of 72 VGPRs).
-  const uint32_t wold4 = (compu(cw, 0) >> 24) | ((compu(cw, 1) >> 24) << 8) | ((compu(cw, 2) >> 24) << 16) |
-                         ((compu(cw, 3) >> 24) << 24);  // the old weights, one byte per voxel
-  float wn[4] = {0.f, 0.f, 0.f, 0.f};
-  int pfast = 0;  // sem_pixel_fast per voxel
+  // follows in pass 3 (above): after both pairs' pass 2, once the pixel records and the other state are dead
+  // (at the end), or (Pairs) directly after its own pair's pass 2 (sem_pair).
+  // what the interleaved pass 3 (Pairs = false) keeps from pass 2; the Pairs form neither writes nor reads them
+  const uint32_t wold4 = Pairs ? 0u
+                               : (compu(cw, 0) >> 24) | ((compu(cw, 1) >> 24) << 8) | ((compu(cw, 2) >> 24) << 16) |
+                                     ((compu(cw, 3) >> 24) << 24);  // the old weights, one byte per voxel
+  float wn[4] = {0.f, 0.f, 0.f, 0.f};  // w_new per voxel (0 where the pair was not updated)
+  int pfast = 0;                       // sem_pixel_fast per voxel
   v2f lnh2[2], lnl2[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -436,8 +477,10 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
       const v2f wr = wc + v2(0x1.fffffep-2f, 0x1.fffffep-2f);
       c0 |= weight_round_cap(wr.x, 40u) << 24;
       c1 |= weight_round_cap(wr.y, 40u) << 24;
-      wn[j0] = w_new.x;
-      wn[j1] = w_new.y;
+      if (!Pairs) {
+        wn[j0] = w_new.x;
+        wn[j1] = w_new.y;
+      }
       if (a0) {
         setc(ts, j0, tq.x);
         setu(cw, j0, c0);
@@ -447,24 +490,21 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
         setu(cw, j1, c1);
       }
       upd_mask |= (a0 ? 1 << j0 : 0) | (a1 ? 1 << j1 : 0);
+      if (Pairs) sem_pair(pr, j0, j1, a0, a1, pf0, pf1, w_old, w_new, wc, iwc, lnh, lnl);
     }
-    lnh2[k] = lnh;
-    lnl2[k] = lnl;
-    pfast |= (pf0 ? 1 << j0 : 0) | (pf1 ? 1 << j1 : 0);
+    if (!Pairs) {
+      lnh2[k] = lnh;
+      lnl2[k] = lnl;
+      pfast |= (pf0 ? 1 << j0 : 0) | (pf1 ? 1 << j1 : 0);
+    }
     mn = fminf(mn, fminf(fabsf(comp(ts, j0)), fabsf(comp(ts, j1))));
   }
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- pass 3: semantic fusion (voxel_tsdf.cu:196-202), the reference's float chain operation for
-  // operation:
-  //   P = expf((w_old logf(p) + w_new logf(ht)) / wc), N = expf((w_old logf(1 - p) + w_new logf(lt)) / wc),
-  //   p' = P / (P + N)
-  // (logf / expf: the oracle's fixed algorithms, sem_logf / sem_expf; the quotients IEEE-exact). The
-  // fast path runs on both voxels of a pair; a voxel whose operands leave its range -- p 0 or 1, ht or
-  // lt 0, extreme quotients -- is recomputed with every special case (sem_update_exact).
-  // both pairs' fast chains first, with no branch between them (the compiler interleaves the two
-  // dependency chains: +0.3 % frames/s, the update span -1 us, same box), then the rare exact
-  // recomputations
-  {
+  if (!Pairs) {
+    // ---- pass 3 of both pairs (the chain described at sem_pair), from what pass 2 left in wold4, wn[], pfast,
+    // lnh2 / lnl2. Both pairs' fast chains first, with no branch between them (the compiler interleaves the two
+    // dependency chains: +0.3 % frames/s, the update span -1 us, same box, at 6 waves per SIMD; the two chains'
+    // registers are what keeps this form out of 72 VGPRs), then the rare exact recomputations.
+    __builtin_amdgcn_sched_barrier(0);
     v2f pn2[2], pv2[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -518,12 +558,12 @@ __device__ __forceinline__ void update_finish(const UpdConst& C, const VisRec& r
   my_upd += __popc(upd_mask);
 }
 
-template <bool Raw, bool Lanes>
+template <bool Raw, bool Lanes, bool Pairs>
 __device__ __forceinline__ void update_block(const UpdConst& C, const VisRec& r, int lane, int hf, float& mn,
                                              int& my_upd) {
   UpdState S;
   update_issue<Raw>(C, r, lane, hf, S);
-  update_finish<Raw, Lanes>(C, r, lane, hf, S, mn, my_upd);
+  update_finish<Raw, Lanes, Pairs>(C, r, lane, hf, S, mn, my_upd);
 }
 
 // The concatenated band lists: band i holds visible-block indices [start_i, start_i + count_i).
@@ -562,7 +602,7 @@ __device__ __forceinline__ size_t band_find(const EngineDev& D, int bst, int lan
 // Raw: a shard's frame -- the pixel terms come from the raw frame (depth, rgb, ht, lt gathers) and
 // are computed per voxel with the ingest's operations (pixel_w_new, sem_logf of ht / lt, the range of
 // pixel_ray), instead of from pixel records packed for the whole frame.
-#ifndef TSDF_INTEGRATE_WAVES  // 6: the semantic update's chain (pass 3) spills the update loop at 7
+#ifndef TSDF_INTEGRATE_WAVES  // 6: these kernels keep the interleaved pass 3 (update_finish), which spills the loop at 7
 #define TSDF_INTEGRATE_WAVES 6
 #endif
 // nint: the update's workgroups (the whole grid). L: the LDS of the last arriver's carving resolve.
@@ -623,7 +663,7 @@ __device__ __forceinline__ bool integrate_body(const EngineDev& D, const FramePa
       } else {
         r = vis[band_find_n(nblocks, bst, lane, b)];
       }
-      update_block<Raw, Lanes>(C, r, lane, hf, mn, my_upd);
+      update_block<Raw, Lanes, false>(C, r, lane, hf, mn, my_upd);
     }
     mn = wave_min_u(mn);
     if (lane == 0) s_min[wave] = mn;
@@ -1092,7 +1132,7 @@ __device__ __forceinline__ void pipe_head(const EngineDev& D, const FrameParams&
     int32_t* ncand = reinterpret_cast<int32_t*>(D.pipe + kPipeNCand + 16 * (f & 1u));
     if (!fast) {
       if (A.cands_in) merge_cands_inbox(D, cand, ncand, A.cands_in, A.cand_cap, A.nshard, s_base);
-      resolve_delete_wg(D, cand, ncand, 0, U.del, f, A.has_alloc ? A.fid_alloc : 0u);
+      resolve_delete_wg<true>(D, cand, ncand, 0, U.del, f, A.has_alloc ? A.fid_alloc : 0u);
     }
     lds_barrier();
     // the carved frame's candidate count and band counts start empty for frame fid_carve + 2 / + 3
@@ -1163,6 +1203,18 @@ __device__ __forceinline__ void wave_wait_tag(const unsigned long long* flag, ui
 __device__ __forceinline__ bool lane_kept(uint32_t* rtag, int32_t idx, uint32_t fc) {
   return __hip_atomic_fetch_or(&rtag[idx], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != fc;
 }
+// the set bits of m below this lane (a ballot's prefix count: the lane's slot in a compacted list), by
+// v_mbcnt: no per-lane mask of the lower lanes held across the record loop
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// a per-lane value as the collection sees it: a copy the optimiser cannot hoist, with everything computed
+// from it, out of the collection loop and so across the record loop (where such invariants -- a lane's
+// list offsets, its LDS addresses -- were spilled to scratch once the loop had 72 VGPRs)
+__device__ __forceinline__ int loop_local(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 // (D: the base view; frame b's lists are addressed through scalar pointers here -- an EngineDev view
 // copied by value, or captured by reference in a lambda, can be materialised in scratch)
 __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParams& P, const PipeArgs& A, int kind, int wi,
@@ -1173,7 +1225,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   VisRec* s_cand = L.cand;  // this workgroup's carve candidates
   VisRec* s_def = L.def;    // deferred (candidate of frame b - 1) blocks
   VisRec* s_list = L.list;  // the records of one collection
-  const int lane = lane_id();
+  const int lane_w = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = wave >> 1, hf = wave & 1;
   const bool t0 = threadIdx.x == 0;
@@ -1190,7 +1242,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   int nvis = 0, nband = 0, p = 0, p_hi = 0, pstep = 1;
   bool carved_known = false;
   if (kind == 0) {
-    bst = band_starts_p(D.band + (size_t)(fb % 3u) * kBands * kBandStride, lane, &nvis);
+    bst = band_starts_p(D.band + (size_t)(fb % 3u) * kBands * kBandStride, lane_w, &nvis);
     nband = nvis;
     if (A.fresh_ready) nvis += D.ctr->n_fresh;
     // group g = blockIdx % 8 (one XCD) takes the g-th contiguous eighth of the pairs in band order
@@ -1209,7 +1261,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   }
   const bool chk = A.has_carve && kind == 0;
   const uint32_t* ct = D.ctag + (size_t)(fc & 1u) * D.nblocks;
-  int my_upd = 0, my_vis = 0, ndef = 0;
+  int my_upd = 0;
   bool def_done = false;
   const bool fresh_co = kind != 0;  // (written in this launch)
   // the collection is wave 0's: one record per lane (its list record and candidate tag gathered
@@ -1222,8 +1274,10 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
   uint32_t& s_fb = L.fb;   // fb for the candidate path (read from LDS: in a register the
                            // frame id was spilled to scratch, reloaded behind a vmcnt(0))
   if (t0) s_fb = fb;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
   if (t0) s_ndef = 0;  // (ordered before its first read by the loop's barrier)
+  // the visible-record count of each pair of waves and wave 0's count of deferred candidates are kept in
+  // LDS (s_vis, s_ndef), not in registers carried around the record loop
+  if (lane_w == 0) s_vis[wave] = 0;
   const UpdConst C = upd_const<false>(D, P);
   // (what the collection and the candidate path read from the arguments, likewise: the loop re-loads none)
   const VisRec* fresh_vis = uniform_reg(D.fresh_vis);
@@ -1239,6 +1293,8 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     if (p < p_hi) {
       const int npr = min((p_hi - p + pstep - 1) / pstep, kPipeList / 2);  // pairs in this collection
       if (wave == 0) {
+        const int lane = loop_local(lane_w);
+        int ndef = __builtin_amdgcn_readfirstlane(s_ndef);  // (wave 0's own store of the previous collection)
         const int b = 2 * (p + (lane >> 1) * pstep) + (lane & 1);
         const bool valid = lane < 2 * npr && b < nvis;
         // the band of list index b: the last band whose start is <= b (starts non-decreasing)
@@ -1264,8 +1320,8 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
         if (cm) {
           const int nc = __popcll(cm);
           if (!carved_known && ndef + nc <= kPipeDefer) {  // deferred to the end
-            if (cand) s_def[ndef + __popcll(cm & lt_mask)] = r;
-            ndef += nc;
+            if (cand) s_def[ndef + lanes_below(cm)] = r;
+            ndef = __builtin_amdgcn_readfirstlane(ndef + nc);  // (wave 0's count, a scalar)
           } else {
             if (!carved_known) wave_wait_tag(carved, tag, status);
             carved_known = true;
@@ -1273,7 +1329,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
           }
         }
         const unsigned long long tm = __ballot(take);
-        if (take) s_list[__popcll(tm & lt_mask)] = r;
+        if (take) s_list[lanes_below(tm)] = r;
         s_pdone[lane] = 0;
         if (lane == 0) {
           s_n = __popcll(tm);
@@ -1281,8 +1337,11 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
         }
       }
       p += npr * pstep;
-    } else if (!def_done && s_ndef > 0) {  // (s_ndef: read before the next collection's barrier)
+    } else if (!def_done && __builtin_amdgcn_readfirstlane(s_ndef) > 0) {  // (s_ndef: read before the next collection's
+                                                                            // barrier; workgroup-uniform, tested as a scalar)
       if (wave == 0) {
+        const int lane = loop_local(lane_w);
+        const int ndef = __builtin_amdgcn_readfirstlane(s_ndef);
         if (!carved_known) wave_wait_tag(carved, tag, status);
         carved_known = true;
         bool take = false;
@@ -1292,7 +1351,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
           take = lane_kept(rtag, r.idx, fc);
         }
         const unsigned long long tm = __ballot(take);
-        if (take) s_list[__popcll(tm & lt_mask)] = r;
+        if (take) s_list[lanes_below(tm)] = r;
         s_pdone[lane] = 0;
         if (lane == 0) s_n = __popcll(tm);
       }
@@ -1301,7 +1360,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
       break;
     }
     lds_barrier();  // (publishes s_list, s_n, s_ndef)
-    n = s_n;
+    n = __builtin_amdgcn_readfirstlane(s_n);  // (workgroup-uniform: the record loop's bound as a scalar)
 #ifdef TSDF_DIAG_STAMPS
     if (t0 && D.dbg && blockIdx.x < (unsigned)kDiagMaxWg) {  // collect ends: first (3), last (4); records (5)
       unsigned long long* q = D.dbg + ((size_t)8 * kDiagMaxWg + blockIdx.x) * kDiagStamps;
@@ -1314,13 +1373,13 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     // ---- update: the two pairs of waves take records pair, pair + 2, ...; no workgroup barrier: the
     // two waves of a record combine their carve minima through LDS (the second to finish decides), so
     // every wave runs its records at its own pace and one wave's memory waits overlap the others' work
-    if (hf == 0 && n > pair) my_vis += (n - pair + 1) >> 1;  // (the records of this pair of waves, below)
+    if (hf == 0 && n > pair && lane_w == 0) s_vis[wave] += (n - pair + 1) >> 1;  // (the records of this pair of waves, below)
     for (int k = pair; k < n; k += 2) {
       const VisRec r = s_list[k];
       float mn = __builtin_nanf("");  // (an all-NaN block's minimum stays NaN: see update_block)
-      update_block<false, true>(C, r, lane, hf, mn, my_upd);
+      update_block<false, true, true>(C, r, lane_w, hf, mn, my_upd);
       mn = wave_min_u(mn);
-      if (lane == 0) {
+      if (lane_w == 0) {
         s_pmin[2 * k + hf] = mn;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");  // (LDS only: pool stores stay in flight)
         if (atomicAdd(&s_pdone[k], 1) == 1) {  // the record's other half is done too
@@ -1343,17 +1402,15 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
     }
   }
   // the workgroup's carve candidates (read by the next launch's carving) and statistics
-  const int tot = wave_sum(my_upd);
-  if (lane == 0) {
-    s_upd[wave] = tot;
-    s_vis[wave] = my_vis;
-  }
+  const int tot = wave_sum_u(my_upd);
+  const int lane = loop_local(lane_w);
+  if (lane == 0) s_upd[wave] = tot;
   lds_barrier();
   const int nc = min(s_ncand, kIntegrateCandBuf);
   if (wave == 0 && nc > 0) {
     int k0 = 0;
     if (lane == 0) k0 = atomicAdd(ncand, nc);
-    k0 = __shfl(k0, 0, 64);
+    k0 = __builtin_amdgcn_readfirstlane(k0);  // (lane 0's)
     if (lane < nc && k0 + lane < D.cand_cap) st_rec_co(&cand[k0 + lane], s_cand[lane]);
   }
   if (t0) {
@@ -1376,7 +1433,7 @@ __device__ __forceinline__ void pipe_update(const EngineDev& D, const FrameParam
 }
 
 #ifndef TSDF_FRAME_WAVES
-#define TSDF_FRAME_WAVES TSDF_INTEGRATE_WAVES
+#define TSDF_FRAME_WAVES 7
 #endif
 // grid: kPipeHead head workgroups (0: carving + allocation), A.nint update workgroups (listed blocks),
 // kPipeFreshWG (this launch's new blocks), then frame c's A.tiles pixel tiles and kVisWorkgroups

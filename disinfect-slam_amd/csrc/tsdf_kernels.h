@@ -114,7 +114,7 @@ constexpr int kPipeAPub = kPipeIngEnd + 32;     // + 16 p: allocation published 
 constexpr int kPipeStats = 512;                 // + 1024 p + 16 i: payload (blocks << 40 | voxels) and,
 constexpr int kPipeStatLines = 64;              //   at +1, the latest end stamp of update counter i
 constexpr int kPipeWords = kPipeStats + 2 * kPipeStatLines * 16;
-constexpr int kFrameUpdWgsPer4Cu = 11;          // default k_frame update workgroups per four CUs (TSDF_FRAME_UPD_WGS)
+constexpr int kFrameUpdWgsPer4Cu = 12;          // default k_frame update workgroups per four CUs (TSDF_FRAME_UPD_WGS)
 constexpr int kPipeHead = 8;                    // workgroups before the update's (0: carving + allocation)
 #ifndef TSDF_PIPE_FRESH_WG  // (an experiment build overrides it)
 #define TSDF_PIPE_FRESH_WG 64

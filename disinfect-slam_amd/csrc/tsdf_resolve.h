@@ -783,6 +783,8 @@ __device__ __forceinline__ void resolve_alloc_wg(const EngineDev& D, const Frame
 // ---------------------------------------------------------------------------------------------
 struct DeleteLds {
   alignas(16) unsigned long long batch[kRB + 2];  // (entry << 32) | hint << 9 | p, ascending (+ pad)
+  // (bkey and u.tmp also carry resolve_delete_fast<true>'s per-candidate state across its barrier: that path
+  // must not use either for anything else)
   unsigned long long bkey[kRB];   // packed key at position p
   int32_t bidx0[kRB];             // slot 0's pool index when the hint says slot 0 holds the key
   union {
@@ -814,6 +816,11 @@ __device__ __forceinline__ void carved_key(const EngineDev& D, uint32_t e, int16
   const unsigned long long w = D.fo[e];
   if ((uint32_t)(w >> 32) == ~fo_fid) nk_insert(D, pack_key(x, y, z), (uint32_t)w);
 }
+// LdsState (k_frame's head): the candidates' state crosses the barrier in LDS (bkey: the record's key word;
+// u.tmp: A and the pool index; neither is used by this path otherwise), not in registers. The compiler lays
+// the ordered rounds out between the loads and the deletes, and at k_frame's 72 VGPRs it spilled that state
+// to scratch across them (24 B). The other callers keep it in registers.
+template <bool LdsState = false>
 __device__ __forceinline__ bool resolve_delete_fast(const EngineDev& D, int n, int free0, uint32_t epoch, int direct,
                                     const unsigned long long (&a)[2], DeleteLds& L, unsigned long long tick0,
                                     uint32_t rel_fid, uint32_t fo_fid) {
@@ -839,6 +846,13 @@ __device__ __forceinline__ bool resolve_delete_fast(const EngineDev& D, int n, i
     idx[r] = in0 ? s0.idx : s1.idx;
     rel[r] = (in0 || head) && local_idx(idx[r]);
   }
+  if (LdsState) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      L.bkey[t + r * kRT] = a[r];
+      L.u.tmp[t + r * kRT] = ((unsigned long long)A[r] << 32) | (uint32_t)idx[r];
+    }
+  }
   uint32_t* ev = reinterpret_cast<uint32_t*>(L.batch);  // entries of the released candidates
   ev[t] = rel[0] ? entry[0] : 0xFFFFFFFFu;
   ev[t + kRT] = rel[1] ? entry[1] : 0xFFFFFFFFu;
@@ -857,6 +871,17 @@ __device__ __forceinline__ bool resolve_delete_fast(const EngineDev& D, int n, i
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     if (t + r * kRT >= n) continue;
+    if (LdsState) {  // (this thread's own words; every candidate is in slot 0 or a head here, so rel[r] is
+                     // local_idx(idx[r]) and entry[r] is cur)
+      const unsigned long long ar = L.bkey[t + r * kRT], st = L.u.tmp[t + r * kRT];
+      A[r] = (uint32_t)(st >> 32);
+      idx[r] = (int32_t)(uint32_t)st;
+      rel[r] = local_idx(idx[r]);
+      x[r] = (int16_t)(ar & 0xFFFF);
+      y[r] = (int16_t)((ar >> 16) & 0xFFFF);
+      z[r] = (int16_t)((ar >> 32) & 0xFFFF);
+      entry[r] = 2 * (A[r] & 0x7FFFFFFFu) + (A[r] >> 31);
+    }
     const uint32_t cur = 2 * (A[r] & 0x7FFFFFFFu) + (A[r] >> 31);
     store_off_idx_co(D.table, cur, 0, -1);
     atomicAnd(&D.occ[cur >> 6], ~(1ull << (cur & 63)));
@@ -892,6 +917,7 @@ __device__ __forceinline__ bool resolve_delete_fast(const EngineDev& D, int n, i
 // rel_fid / fo_fid: pipelined frames (released_block above). The deletes are ordered by the entry each
 // candidate holds in the table NOW (its record's entry may predate an earlier carving that moved a list
 // element into its bucket's head).
+template <bool LdsState = false>  // (resolve_delete_fast's)
 __device__ __forceinline__ void resolve_delete_wg(const EngineDev& D, const VisRec* __restrict__ recs,
                                   const int32_t* __restrict__ count, int direct, DeleteLds& L,
                                   uint32_t rel_fid = 0u, uint32_t fo_fid = 0u) {
@@ -912,7 +938,7 @@ __device__ __forceinline__ void resolve_delete_wg(const EngineDev& D, const VisR
     b1 = ld_co(&rq[2 * (t + kRT) + 1]);
     if (!resolve_fast_off()) {
       const unsigned long long a[2] = {a0, a1};
-      if (resolve_delete_fast(D, n, free0, epoch, direct, a, L, tick0, rel_fid, fo_fid)) return;
+      if (resolve_delete_fast<LdsState>(D, n, free0, epoch, direct, a, L, tick0, rel_fid, fo_fid)) return;
       lds_barrier();  // fallback: the ordered rounds below reuse the LDS the fast path used
     }
   }
